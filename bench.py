@@ -71,6 +71,9 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--repeats", type=int, default=9,
                     help="the timed region of --steps steps is run this many times; the line reports the median")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (bus, vec) and a seeded sample of the bank's phases "
+                         "after it to DIR/<name>.npy (float64 / float32, at most 44 MiB)")
     return ap.parse_args()
 
 
@@ -859,6 +862,36 @@ def multi_gpu_legs(sta, synthetic, tab, rdzv, rank, world, local, verify, L):
 
 
 # ---------------------------------------------------------------------------------------------
+DUMP_FRAMES = 1 << 20                 # --dump-outputs: at most 8 + 4 MiB of bus and vec, 32 MiB of phases
+DUMP_VOICES = 1 << 22
+DUMP_SEED = 0x5EED0D0D
+
+
+def dump_sample(x, cap):
+    """x itself when it has at most `cap` elements, else `cap` of them at fixed, seeded, sorted positions."""
+    if len(x) <= cap:
+        return x
+    return x[np.sort(np.random.default_rng(DUMP_SEED).choice(len(x), cap, replace=False))]
+
+
+def dump_outputs(saw, frames, out_dir):
+    """--dump-outputs: what the timed path handed back in its last step -- the bus (int32, exact in float64) and the
+    float block of smx_bank_fetch -- and the phases that step left in the bank (smx_bank_read; uint32, exact in
+    float64), as DIR/<name>.npy.  Runs after the timed regions on every rank (the fetch issues any queued all-reduce,
+    a collective); only rank 0 writes.  The inputs depend on the arguments alone, so two builds run with the same
+    arguments can be compared output for output."""
+    bus, vec = saw.bank.fetch(frames)
+    _, phase = saw.bank.read()
+    if out_dir is None:
+        return
+    out = {"bus": dump_sample(bus, DUMP_FRAMES).astype(np.float64),
+           "vec": dump_sample(vec, DUMP_FRAMES).astype(np.float32),
+           "phase": dump_sample(phase, DUMP_VOICES).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def run_rank(a):
     # stdout carries exactly ONE line (the JSON): libraries that print banners at init (RCCL
     # prints its version block to stdout) are pointed at stderr for the whole run.
@@ -926,6 +959,8 @@ def run_rank(a):
         regions.append((max(p[0] for p in per_rank), max(p[1] for p in per_rank), [p[1] for p in per_rank]))
     regions.sort(key=lambda r: r[0])
     dt, kernel_ms, kernel_ms_ranks = regions[len(regions) // 2]
+    if a.dump_outputs:
+        dump_outputs(saw, a.frames, a.dump_outputs if rank == 0 else None)
     dt_min, dt_max = regions[0][0], regions[-1][0]
 
     # the timed kernel's only output is the bus: one more step, compared with the closed form

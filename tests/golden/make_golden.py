@@ -19,6 +19,8 @@ for the pdm.h vectors): `python tests/golden/make_golden.py`.
                             (stm32f103/mod_pdm.c:159-175, oracle/_ref/libref_pwmosc.so): the reference's
                             default speed 256*13 and five others, 70 000 ticks each, hard syncs at
                             scripted ticks.
+ live_reference.npz         what the four compiled reference units above answer to the seeded random
+                            inputs of the randomised oracle-vs-reference tests (tests/refcases.py).
 """
 import json
 import os
@@ -286,6 +288,27 @@ def pwmosc_reference():
     np.savez_compressed(os.path.join(HERE, "pwmosc_reference.npz"), **out)
 
 
+def live_reference():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import refcases
+    refs = {k: getattr(oracle, "load_ref_" + k)() for k in ("pwmosc", "synth", "pmeas", "pdm")}
+    if any(r is None for r in refs.values()):
+        print("oracle/_ref absent (the reference sources are not available to oracle/Makefile): live_reference skipped")
+        return
+    out = {"_provenance": np.array("answers of the reference units compiled verbatim into oracle/_ref (oracle/Makefile "
+                                   "ref) to the seeded inputs of tests/refcases.py")}
+    out["pwm_duty"], out["pwm_phase_end"] = refcases.pwm_on_reference(
+        refs["pwmosc"], refcases.pwm_cases(refcases.rng(refcases.PWM_SEED, False)))
+    for k, v in refcases.synth_on_reference(
+            refs["synth"], refcases.synth_ops(refcases.rng(refcases.SYNTH_SEED, False))).items():
+        out["synth_" + k] = v
+    out["pmeas_steps"], out["pmeas_end"] = refcases.pmeas_on_reference(
+        refs["pmeas"], refcases.pmeas_cases(refcases.rng(refcases.PMEAS_SEED, False)))
+    out["pdm_q"], out["pdm_state_end"] = refcases.pdm_on_reference(
+        refs["pdm"], refcases.pdm_cases(refcases.rng(refcases.PDM_SEED, False)))
+    np.savez_compressed(refcases.GOLD_FILE, **out)
+
+
 if __name__ == "__main__":
     survey_known_answers()
     pdm_h_reference()
@@ -293,4 +316,5 @@ if __name__ == "__main__":
     synth_c_reference()
     pmeas_reference()
     pwmosc_reference()
+    live_reference()
     print(sorted(os.listdir(HERE)))

@@ -96,3 +96,13 @@ def test_roof_and_wrap_helpers():
     assert abs(r["hbm_frac"] - 1.0) < 1e-3 and r["bound"] == "hbm"
     r = bench.roof(1.0, 1.0, units=64 * bench.SIMD_CYCLES_PER_S * 1e-3, issue_cycles=1.0)
     assert abs(r["valu_issue_frac"] - 1.0) < 1e-3 and r["bound"] == "vector issue"
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded():
+    """--dump-outputs: a bank larger than the cap is sampled at the same sorted positions on every run; a smaller
+    one is written whole; what the dump holds fits its 64 MB bound."""
+    x = np.arange(1000, dtype=np.uint32)
+    assert bench.dump_sample(x, 1000) is x
+    a, b = bench.dump_sample(x, 100), bench.dump_sample(x.copy(), 100)
+    assert len(a) == 100 and np.array_equal(a, b) and np.all(np.diff(a.astype(np.int64)) > 0)
+    assert bench.DUMP_FRAMES * (8 + 4) + bench.DUMP_VOICES * 8 <= 64 * 10**6

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle
+import refcases
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -270,27 +271,23 @@ def test_pdm_h_survey_known_answers(orc, kat):
 
 
 def test_pdm_h_live_against_real_header(orc):
-    """Random inputs against the reference's own pdm.h compiled into oracle/_ref
-    (present in the build container; travels to the GPU box as a .so)."""
+    """Random inputs against the reference's own pdm.h compiled into oracle/_ref when it is present (it travels
+    with the built tree as a .so), else against its recorded answers to the committed seed
+    (tests/golden/live_reference.npz, tests/refcases.py)."""
     ref = oracle.load_ref_pdm()
-    if ref is None:
-        pytest.skip("oracle/_ref/libref_pdm.so not built (needs /root/reference)")
-    rng = np.random.default_rng(1234)
-    for order in (1, 2, 3, 4):
-        fo = getattr(orc, "orc_pdm%d_update" % order)
-        fr = getattr(ref, "ref_pdm%d_update" % order)
-        for _ in range(20):
-            so = rng.integers(0, 2**32, order, dtype=np.uint64).astype(np.uint32)
-            sr = so.copy()
-            sh = int(rng.integers(1, 32))
-            for t in range(300):
-                x = int(rng.integers(0, 2**32))
-                d = int(rng.integers(0, 2**32)) if t % 3 else 0
-                if order == 1:
-                    assert fo(so, x, sh) == fr(sr, x, sh)
-                else:
-                    assert fo(so, x, sh, d) == fr(sr, x, sh, d)
-            assert np.array_equal(so, sr)
+    g = refcases.recorded()
+    cases = refcases.pdm_cases(refcases.rng(refcases.PDM_SEED, ref is not None))
+    want_q, want_s = g["pdm_q"], g["pdm_state_end"]
+    if ref is not None:
+        live_q, live_s = refcases.pdm_on_reference(ref, cases)
+        if not refcases.soaking():
+            assert np.array_equal(live_q, want_q) and np.array_equal(live_s, want_s), \
+                "tests/golden/live_reference.npz is stale (tests/golden/make_golden.py)"
+        want_q, want_s = live_q, live_s
+    q, s = refcases.pdm_on_oracle(orc, cases)
+    for k, (order, _, sh, _, _) in enumerate(cases):
+        assert np.array_equal(q[k], want_q[k]), (order, sh, k)
+        assert np.array_equal(s[k], want_s[k]), (order, sh, k)
 
 
 # ---- mod_pdm_pwm.c / mod_controlrate.c / pmeas.h / cproc.h: restatement checks --

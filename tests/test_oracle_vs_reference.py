@@ -6,8 +6,9 @@ compile verbatim with system headers alone
 (oracle/Makefile `ref` streams those line ranges into gcc; nothing is stubbed).  Their
 outputs are committed as tests/golden/synth_c_reference.npz / pmeas_reference.npz / pwmosc_reference.npz
 (generator: tests/golden/make_golden.py) and the oracle must reproduce them bit for bit;
-when oracle/_ref is present (build container, and the GPU box: the .so travels) the oracle
-is also compared live on random operation sequences.
+the oracle is also compared on random operation sequences: live when oracle/_ref is present
+(it travels with the built tree), else against the reference's recorded answers to the committed
+seeds (tests/golden/live_reference.npz, tests/refcases.py).
 """
 import ctypes as C
 import json
@@ -17,6 +18,7 @@ import numpy as np
 import pytest
 
 import oracle
+import refcases
 import replay
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -124,86 +126,53 @@ def test_oracle_pwm_update_reproduces_reference_outputs(orc):
         assert int(g[name + "_wraps"]) >= 19, name          # the 24-bit mask (mod_pdm.c:162) is crossed many times
 
 
-# ---- live, when the compiled reference is present ----------------------------------------
+# ---- random inputs: live when the compiled reference is present, else its recorded answers ----------
+# (tests/refcases.py; the answers to the committed seeds are tests/golden/live_reference.npz)
+def _want(ref, on_reference, cases_of, seed, recorded):
+    """-> (inputs, the reference's answers to them): live from oracle/_ref when it is there (and then the recorded
+    answers must be what it gives), else the committed seed's inputs and the recorded answers."""
+    live = ref is not None
+    cases = cases_of(refcases.rng(seed, live))
+    if not live:
+        return cases, recorded
+    want = on_reference(ref, cases)
+    if not refcases.soaking():
+        for w, r in zip(want if isinstance(want, tuple) else want.values(),
+                        recorded if isinstance(recorded, tuple) else recorded.values()):
+            assert np.array_equal(w, r), "tests/golden/live_reference.npz is stale (tests/golden/make_golden.py)"
+    return cases, want
+
+
 def test_live_random_pwm_updates_against_compiled_mod_pdm_c(orc):
-    ref = oracle.load_ref_pwmosc()
-    if ref is None:
-        pytest.skip("oracle/_ref/libref_pwmosc.so not built (needs /root/reference)")
-    rng = np.random.default_rng(159175)
-    for case in range(40):
-        nt = 5000
-        phase0 = int(rng.integers(0, 1 << 24))
-        speed = int(rng.integers(0, 1 << int(rng.integers(1, 33))))
-        sync = (rng.random(nt) < rng.choice([0.0, 0.001, 0.05])).astype(np.uint8)
-        ref.ref_pwm_set(phase0, speed)
-        want = np.zeros(nt, np.uint8)
-        ref.ref_pwmosc_run(nt, sync.ctypes.data, want.ctypes.data, None)
-        phase = np.array([phase0], np.uint32)
-        got = np.zeros((nt, 1), np.uint8)
-        sync_words = np.ascontiguousarray(sync.astype(np.uint32).reshape(nt, 1))     # kept alive across the call
-        orc.orc_pwmosc_run(phase, np.array([speed], np.uint32), 1, sync_words.ctypes.data, nt, got.ctypes.data)
-        assert np.array_equal(got[:, 0], want), case
-        assert int(phase[0]) == ref.ref_pwm_get_phase(), case
+    g = refcases.recorded()
+    cases, (want_duty, want_phase) = _want(oracle.load_ref_pwmosc(), refcases.pwm_on_reference, refcases.pwm_cases,
+                                           refcases.PWM_SEED, (g["pwm_duty"], g["pwm_phase_end"]))
+    duty, phase = refcases.pwm_on_oracle(orc, cases)
+    for case in range(len(cases)):
+        assert np.array_equal(duty[case], want_duty[case]), case
+        assert phase[case] == want_phase[case], case
 
 
 def test_live_random_ops_against_compiled_synth_c(orc):
-    ref = oracle.load_ref_synth()
-    if ref is None:
-        pytest.skip("oracle/_ref/libref_synth.so not built (needs /root/reference)")
-    rng = np.random.default_rng(20261004)
-    x = oracle.RefSynth()
-    ref.synth_init(C.byref(x))
-    n2v = np.zeros(128, np.int32)
-    inc = np.zeros(64, np.uint32)
-    st = np.zeros(64, np.uint32)
-    with oracle.quiet_stderr():
-        for i in range(3000):
-            r = rng.random()
-            if r < 0.35:
-                n = int(rng.integers(0, 1024))
-                ref.synth_note_on(C.byref(x), n)
-                orc.orc_note_on(n2v, inc, 64, n)
-            elif r < 0.6:
-                n = int(rng.integers(0, 1024))
-                ref.synth_note_off(C.byref(x), n)
-                orc.orc_note_off(n2v, inc, 64, n)
-            elif r < 0.65:
-                for v in range(64):
-                    val = int(rng.integers(0, 2**32))
-                    x.voice[v].note_state = val
-                    st[v] = val
-            elif r < 0.7:
-                assert ref.sum_tick_square(C.byref(x)) == orc.orc_sum_tick_square(inc, st, 64)
-            elif r < 0.72:
-                assert ref.voice_alloc(C.byref(x)) == orc.orc_voice_alloc(inc, 64)
-            else:
-                nf = int(rng.choice([1, 2, 7, 64, 300]))
-                want = np.zeros(nf, np.float32)
-                ref.synth_run(C.byref(x), want, nf)
-                _, got = oracle.synth_run(orc, inc, st, nf)
-                assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), i
-            if i % 100 == 0:
-                rn2v, rinc, rst = x.arrays()
-                assert np.array_equal(rn2v, n2v) and np.array_equal(rinc, inc) and np.array_equal(rst, st)
-    rn2v, rinc, rst = x.arrays()
-    assert np.array_equal(rn2v, n2v) and np.array_equal(rinc, inc) and np.array_equal(rst, st)
+    g = refcases.recorded()
+    rec = {k: g["synth_" + k] for k in ("run_bits", "square_bits", "alloc", "snapshots")}
+    ops, want = _want(oracle.load_ref_synth(), refcases.synth_on_reference, refcases.synth_ops,
+                      refcases.SYNTH_SEED, rec)
+    got = refcases.synth_on_oracle(orc, ops)
+    for k in rec:
+        assert got[k].shape == want[k].shape, k
+        diff = got[k] != want[k]
+        bad = np.flatnonzero(diff.any(axis=1) if diff.ndim > 1 else diff)
+        assert len(bad) == 0, (k, int(bad[0]))
 
 
 def test_live_random_timestamps_against_compiled_pmeas_h(orc):
-    ref = oracle.load_ref_pmeas()
-    if ref is None:
-        pytest.skip("oracle/_ref/libref_pmeas.so not built (needs /root/reference)")
-    rng = np.random.default_rng(77)
-    for lm in (8, 12, 20, 26, 30):
-        r = oracle.RefPmeas(ref, lm)
-        p = oracle.Pmeas(log_max=lm)
-        cc = 0
-        for i in range(4000):
-            cc = (cc + int(rng.integers(1, 1 << int(rng.integers(1, lm + 2))))) & 0xFFFFFFFF
-            r.update(cc)
-            orc.orc_pmeas_update(C.byref(p), cc)
-            assert (r.get("write"), r.get("num"), r.get("accu"), r.get("last_cc")) == \
-                   (p.write, p.num, p.accu, p.last_cc)
-        assert [r.get("avg0"), r.get("avg1"), r.get("num0"), r.get("num1")] == \
-               [p.avg[0], p.avg[1], p.num_pub[0], p.num_pub[1]]
-        assert p.write > 0
+    g = refcases.recorded()
+    cases, (want_steps, want_end) = _want(oracle.load_ref_pmeas(), refcases.pmeas_on_reference, refcases.pmeas_cases,
+                                          refcases.PMEAS_SEED, (g["pmeas_steps"], g["pmeas_end"]))
+    steps, end = refcases.pmeas_on_oracle(orc, cases)
+    for k, (lm, _) in enumerate(cases):
+        bad = np.flatnonzero((steps[k] != want_steps[k]).any(axis=1))
+        assert len(bad) == 0, (lm, int(bad[0]))
+        assert np.array_equal(end[k], want_end[k]), lm
+        assert steps[k, -1, 0] > 0                      # write
