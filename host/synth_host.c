@@ -24,10 +24,20 @@
  *                                                helpers over pipes, and the library sums the buses (RCCL).
  *                                                SYNTH_DEVICES=0,1,... maps ranks to HIP devices (default: rank r ->
  *                                                device r)
+ *   SYNTH_POLY=262144 synth.dynamic.host.elf     real JACK, the poly voice bank (saw -> LPF -> ADSR -> stereo):
+ *                                                MIDI through smx_poly_midi_events (the device allocates voices:
+ *                                                free voice of lowest index, else the quietest), audio through
+ *                                                smx_poly_run on two ports, "out_l" and "out_r".  Every voice gets
+ *                                                one patch at start: SYNTH_POLY_PATCH="a,ar,dr,sl,rr,pan" (filter
+ *                                                coefficient, per-sample attack/decay rates, sustain level, release
+ *                                                rate, pan_l | pan_r << 16; default
+ *                                                "0.25,0x00800000,0x00040000,0xA0000000,0x00020000,0x00800080").
+ *                                                Not with SYNTH_RANKS.
  *   SYNTH_FAKE_PERIOD_US=1333 ... --fake-jack    pace the scripted callbacks like a sound card
  *   synth.dynamic.host.elf --fake-jack NBLOCKS NFRAMES EVENTS.bin OUT.f32
  *       EVENTS.bin: records {u32 block; u8 size; u8 bytes[3]} delivered to
- *       midi_in at the start of that block; OUT.f32: NBLOCKS*NFRAMES floats.
+ *       midi_in at the start of that block; OUT.f32: NBLOCKS*NFRAMES floats (SYNTH_POLY: per block NFRAMES
+ *       left floats, then NFRAMES right floats).
  */
 #define _GNU_SOURCE
 #include <dlfcn.h>
@@ -78,17 +88,24 @@ static struct {
     struct fake_event *ev; size_t nev, cursor;
     uint32_t block;
     jack_midi_event_t cur[1024]; uint32_t ncur;
-    float *audio;
+    float *audio, *audio_r;
 } fake;
-static jack_port_t *const FAKE_MIDI_PORT = (jack_port_t *)1, *const FAKE_AUDIO_PORT = (jack_port_t *)2;
+static jack_port_t *const FAKE_MIDI_PORT = (jack_port_t *)1, *const FAKE_AUDIO_PORT = (jack_port_t *)2,
+                   *const FAKE_AUDIO_R_PORT = (jack_port_t *)3;
 
-static void *fake_port_get_buffer(jack_port_t *p, jack_nframes_t n) { (void)n; return p == FAKE_AUDIO_PORT ? (void *)fake.audio : (void *)&fake; }
+static void *fake_port_get_buffer(jack_port_t *p, jack_nframes_t n) {
+    (void)n;
+    return p == FAKE_AUDIO_PORT ? (void *)fake.audio : p == FAKE_AUDIO_R_PORT ? (void *)fake.audio_r : (void *)&fake;
+}
 static uint32_t fake_midi_get_event_count(void *b) { (void)b; return fake.ncur; }
 static int fake_midi_event_get(jack_midi_event_t *e, void *b, uint32_t i) { (void)b; if (i >= fake.ncur) return -1; *e = fake.cur[i]; return 0; }
 
 /* ---- SYNTH: either the reference's struct synth or an N-voice bank --------- */
 static struct synth synth;               /* linux/synth.c:208 */
 static smx_bank *bank;                   /* SYNTH_VOICES > 64 */
+static smx_poly *poly;                   /* SYNTH_POLY */
+static float *poly_lr;                   /* interleaved L,R of one block */
+static uint32_t poly_lr_frames;
 
 /* SYNTH_RANKS > 1: this process is rank 0 and the only JACK client; helper[r] is the write end of rank r's pipe. */
 static int n_ranks = 1, my_rank = 0;
@@ -192,6 +209,33 @@ static void helper_loop(int fd, uint32_t voices) {
     _exit(0);
 }
 static jack_port_t *midi_in, *audio_out; /* linux/synth.c:214-221 */
+static jack_port_t *audio_out_r;         /* SYNTH_POLY: audio_out is "out_l", this is "out_r" */
+
+/* SYNTH_POLY: the poly bank, every voice silent with one patch (SYNTH_POLY_PATCH) */
+static void setup_poly(uint32_t voices) {
+    float a = 0.25f;
+    uint32_t ar = 0x00800000u, dr = 0x00040000u, sl = 0xA0000000u, rr = 0x00020000u, pan = 0x00800080u;
+    const char *pp = getenv("SYNTH_POLY_PATCH");
+    if (pp) {
+        char *end;
+        a = strtof(pp, &end);
+        uint32_t *f[5] = { &ar, &dr, &sl, &rr, &pan };
+        for (int i = 0; i < 5; i++) { ASSERT(*end == ','); *f[i] = (uint32_t)strtoul(end + 1, &end, 0); }
+        ASSERT(*end == 0);
+    }
+    ASSERT(voices >= 1 && (poly = smx_poly_create(voices, 0)));
+    float *af = malloc((size_t)voices * 4);
+    uint32_t *u[5];
+    for (int i = 0; i < 5; i++) ASSERT((u[i] = malloc((size_t)voices * 4)));
+    ASSERT(af);
+    const uint32_t val[5] = { ar, dr, sl, rr, pan };
+    for (uint32_t v = 0; v < voices; v++) { af[v] = a; for (int i = 0; i < 5; i++) u[i][v] = val[i]; }
+    struct smx_poly_arrays arr = { 0 };
+    arr.a = af; arr.ar = u[0]; arr.dr = u[1]; arr.sl = u[2]; arr.rr = u[3]; arr.pan = u[4];
+    ASSERT(0 == smx_poly_load(poly, &arr));         /* the rest of the state is zero: silent, idle */
+    free(af);
+    for (int i = 0; i < 5; i++) free(u[i]);
+}
 
 static inline void process_midi(jack_nframes_t nframes) {        /* linux/synth.c:227-260 */
     void *midi_in_buf = jack.port_get_buffer(midi_in, nframes);
@@ -202,16 +246,26 @@ static inline void process_midi(jack_nframes_t nframes) {        /* linux/synth.
         jack_midi_event_t event;
         jack.midi_event_get(&event, midi_in_buf, i);
         const uint8_t *msg = event.buffer;
-        if (!bank) { synth_midi_event(&synth, msg, event.size); continue; }
+        if (!bank && !poly) { synth_midi_event(&synth, msg, event.size); continue; }
         if (event.size != 3) continue;           /* linux/synth.c:236: only 3-byte events */
-        if (nbatch == 4096) { to_helpers(0, batch, 4096); ASSERT(0 == smx_bank_midi_events(bank, batch, nbatch)); nbatch = 0; }
+        if (nbatch == 4096) {
+            if (poly) ASSERT(0 == smx_poly_midi_events(poly, batch, nbatch));
+            else { to_helpers(0, batch, 4096); ASSERT(0 == smx_bank_midi_events(bank, batch, nbatch)); }
+            nbatch = 0;
+        }
         memcpy(batch + 3 * nbatch++, msg, 3);
     }
-    if (nbatch) { to_helpers(0, batch, (uint32_t)nbatch); ASSERT(0 == smx_bank_midi_events(bank, batch, nbatch)); }
+    if (nbatch && poly) ASSERT(0 == smx_poly_midi_events(poly, batch, nbatch));
+    else if (nbatch) { to_helpers(0, batch, (uint32_t)nbatch); ASSERT(0 == smx_bank_midi_events(bank, batch, nbatch)); }
 }
 static inline void process_audio(jack_nframes_t nframes) {       /* linux/synth.c:261-276 */
     jack_default_audio_sample_t *dst = jack.port_get_buffer(audio_out, nframes);
-    if (bank) { to_helpers(nframes, NULL, 0); ASSERT(0 == smx_bank_run(bank, dst, NULL, (int)nframes)); }
+    if (poly) {                                                  /* interleaved L,R -> the two ports */
+        jack_default_audio_sample_t *dst_r = jack.port_get_buffer(audio_out_r, nframes);
+        ASSERT(nframes <= poly_lr_frames);
+        ASSERT(0 == smx_poly_run(poly, poly_lr, NULL, (int)nframes));
+        for (jack_nframes_t i = 0; i < nframes; i++) { dst[i] = poly_lr[2 * i]; dst_r[i] = poly_lr[2 * i + 1]; }
+    } else if (bank) { to_helpers(nframes, NULL, 0); ASSERT(0 == smx_bank_run(bank, dst, NULL, (int)nframes)); }
     else      synth_run(&synth, dst, (int)nframes);
 }
 static int process(jack_nframes_t nframes, void *arg) {          /* linux/synth.c:277-282 */
@@ -249,6 +303,13 @@ int main(int argc, char **argv) {
     const char *voices_env = getenv("SYNTH_VOICES");
     uint32_t voices = voices_env ? (uint32_t)strtoul(voices_env, NULL, 0) : 64;
     uint8_t id[SMX_UNIQUE_ID_BYTES] = {0};
+    const char *poly_env = getenv("SYNTH_POLY");
+    if (poly_env && getenv("SYNTH_RANKS")) { LOG("synth: SYNTH_POLY does not shard over ranks (SYNTH_RANKS)\n"); exit(1); }
+    const uint32_t poly_voices = poly_env ? (uint32_t)strtoul(poly_env, NULL, 0) : 0;
+    if (poly_env) {
+        poly_lr_frames = 8192;                                   /* the largest JACK period taken */
+        ASSERT((poly_lr = malloc(sizeof(float) * 2 * poly_lr_frames)));
+    }
     if (getenv("SYNTH_RANKS") && voices > 64) {
         /* fork the helper ranks FIRST: no process may have touched the GPU when it forks */
         n_ranks = atoi(getenv("SYNTH_RANKS"));
@@ -289,13 +350,15 @@ int main(int argc, char **argv) {
         ASSERT(fread(fake.ev, sizeof(struct fake_event), fake.nev, f) == fake.nev);
         fclose(f);
         fake.audio = malloc(sizeof(float) * nframes);
+        fake.audio_r = malloc(sizeof(float) * nframes);
         fake.on = 1;
         jack.port_get_buffer = fake_port_get_buffer;
         jack.midi_get_event_count = fake_midi_get_event_count;
         jack.midi_event_get = fake_midi_event_get;
         midi_in = FAKE_MIDI_PORT;
         audio_out = FAKE_AUDIO_PORT;
-        setup_bank(voices, id);
+        audio_out_r = FAKE_AUDIO_R_PORT;
+        if (poly_env) setup_poly(poly_voices); else setup_bank(voices, id);
         synth_init(&synth);
         FILE *out = fopen(argv[5], "wb");
         ASSERT(out);
@@ -330,10 +393,11 @@ int main(int argc, char **argv) {
             double us = (tb.tv_sec - ta.tv_sec) * 1e6 + (tb.tv_nsec - ta.tv_nsec) * 1e-3;
             if (fake.block >= 2) { t_sum += us; if (us > t_max) t_max = us; }   /* skip warm-up blocks */
             ASSERT(fwrite(fake.audio, sizeof(float), nframes, out) == nframes);
+            if (poly) ASSERT(fwrite(fake.audio_r, sizeof(float), nframes, out) == nframes);
         }
         fclose(out);
         LOG("synth: fake-jack rendered %u blocks of %u frames, %u voices; process(): mean %.1f us, max %.1f us "
-            "(deadline at 48 kHz: %.0f us)\n", nblocks, nframes, voices,
+            "(deadline at 48 kHz: %.0f us)\n", nblocks, nframes, poly_env ? poly_voices : voices,
             nblocks > 2 ? t_sum / (nblocks - 2) : 0.0, t_max, nframes / 48000.0 * 1e6);
     } else {
         /* Jack client setup: linux/synth.c:285-301 */
@@ -343,8 +407,14 @@ int main(int argc, char **argv) {
         jack_client_t *client = jack.client_open(client_name, JackNullOption, &status);
         ASSERT(client);
         ASSERT(midi_in = jack.port_register(client, "midi_in", JACK_DEFAULT_MIDI_TYPE, JackPortIsInput, 0));
-        ASSERT(audio_out = jack.port_register(client, "audio_out", JACK_DEFAULT_AUDIO_TYPE, JackPortIsOutput, 0));
-        setup_bank(voices, id);
+        if (poly_env) {
+            ASSERT(audio_out = jack.port_register(client, "out_l", JACK_DEFAULT_AUDIO_TYPE, JackPortIsOutput, 0));
+            ASSERT(audio_out_r = jack.port_register(client, "out_r", JACK_DEFAULT_AUDIO_TYPE, JackPortIsOutput, 0));
+            setup_poly(poly_voices);
+        } else {
+            ASSERT(audio_out = jack.port_register(client, "audio_out", JACK_DEFAULT_AUDIO_TYPE, JackPortIsOutput, 0));
+            setup_bank(voices, id);
+        }
         synth_init(&synth);
         jack.set_process_callback(client, process, 0);
         ASSERT(!mlockall(MCL_CURRENT | MCL_FUTURE));

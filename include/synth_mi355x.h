@@ -290,6 +290,34 @@ int smx_poly_sync(smx_poly *p);
 int smx_poly_timer_start(smx_poly *p);
 int smx_poly_timer_stop(smx_poly *p, float *ms);
 
+/* Playing the poly bank: note on/off with envelope-aware voice allocation, run on the device
+ * (DESIGN.md §3.5b).  The bank keeps note2voice[128] (a voice or none) and a note per voice (or
+ * none); a fresh bank has none everywhere.  A voice is FREE when inc == 0, or gate == 0 and
+ * stage == idle, judged on the arrays as they stand at that event.  Events apply one at a time,
+ * in order, ahead of the next block (the block boundary is the only time base); m = note % 128.
+ *   note_on(m):  1. if note2voice[m] is set, release that voice first (as note_off);
+ *                2. pick the free voice of lowest index; if none is free, the voice with the
+ *                   smallest (gate, level, index): a releasing voice before a held one, then the
+ *                   lowest envelope level as of the last block, then the lowest index;
+ *                3. if the voice holds a note k, clear note2voice[k];
+ *                4. if its gate was 1, stage = R (the block start re-attacks it from its level);
+ *                5. inc = note_to_inc(m), gate = 1, voice's note = m, note2voice[m] = voice.
+ *                Phase, y, level, a, ar/dr/sl/rr and pan are left as they are.
+ *   note_off(m): nothing if note2voice[m] is none (unlike the saw bank, no voice-0 quirk); else
+ *                gate = 0 and both maps cleared; inc stays, so the release sounds.
+ *   MIDI:        process_midi's dispatch (linux/synth.c:236-258): 3-byte messages only; 0x90 with
+ *                velocity 0 and 0x80 are note_off, 0x90 otherwise note_on, all else ignored.
+ * smx_poly_load with a non-NULL inc or gate clears both maps.  Negative notes: SMX_E_ARG.
+ * Banks of 2^31 voices or more: SMX_E_RANGE.  All but read_notes queue their work on the bank's
+ * stream without a host sync: a batch is one copy from double-buffered pinned staging and
+ * launches of at most 64 events each; any n_events is accepted, and n calls of
+ * smx_poly_midi_event leave the same state as one smx_poly_midi_events of the same messages. */
+int smx_poly_note_on (smx_poly *p, int note);
+int smx_poly_note_off(smx_poly *p, int note);
+int smx_poly_midi_event (smx_poly *p, const uint8_t *msg, size_t size);
+int smx_poly_midi_events(smx_poly *p, const uint8_t *msgs3, size_t n_events);  /* n 3-byte msgs */
+int smx_poly_read_notes(smx_poly *p, int32_t note2voice[128]);                 /* -1 = none; syncs */
+
 /* ======================================================================== */
 /* 5. Noise-shaped PWM bank: stm32f103/mod_pdm_pwm.c:76-160, pdm.h:10-77,    */
 /*    mod_controlrate.c:28-57                                                */

@@ -138,6 +138,11 @@ ABI = [
     ("smx_poly_sync", C.c_int, [_P]),
     ("smx_poly_timer_start", C.c_int, [_P]),
     ("smx_poly_timer_stop", C.c_int, [_P, C.POINTER(C.c_float)]),
+    ("smx_poly_note_on", C.c_int, [_P, C.c_int]),
+    ("smx_poly_note_off", C.c_int, [_P, C.c_int]),
+    ("smx_poly_midi_event", C.c_int, [_P, _P, C.c_size_t]),
+    ("smx_poly_midi_events", C.c_int, [_P, _P, C.c_size_t]),
+    ("smx_poly_read_notes", C.c_int, [_P, _P]),
     ("smx_pwm_create", _P, [C.c_uint32, C.c_int, C.c_int]),
     ("smx_pwm_destroy", None, [_P]),
     ("smx_pwm_config", C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -484,6 +489,27 @@ class PolyBank:
         ms = C.c_float()
         _check(lib().smx_poly_timer_stop(self._h, C.byref(ms)), "smx_poly_timer_stop")
         return ms.value
+
+    def note_on(self, note):
+        _check(lib().smx_poly_note_on(self._h, note), "smx_poly_note_on")
+
+    def note_off(self, note):
+        _check(lib().smx_poly_note_off(self._h, note), "smx_poly_note_off")
+
+    def midi_event(self, msg):
+        m = np.ascontiguousarray(msg, np.uint8)
+        _check(lib().smx_poly_midi_event(self._h, _ptr(m), len(m)), "smx_poly_midi_event")
+
+    def midi_events(self, msgs):
+        """All 3-byte MIDI events of a block at once: msgs is (n, 3) uint8."""
+        m = np.ascontiguousarray(msgs, np.uint8).reshape(-1, 3)
+        _check(lib().smx_poly_midi_events(self._h, _ptr(m), len(m)), "smx_poly_midi_events")
+
+    def read_notes(self):
+        """-> note2voice int32[128], -1 = none (syncs)"""
+        out = np.empty(128, np.int32)
+        _check(lib().smx_poly_read_notes(self._h, _ptr(out)), "smx_poly_read_notes")
+        return out
 
 
 PWM_FIELDS = ("setpoint", "pos0", "vel0", "pos1", "vel1", "s1", "s2", "s3", "s4")

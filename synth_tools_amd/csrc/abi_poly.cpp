@@ -17,6 +17,18 @@ struct smx_poly {
     int32_t *h_bus = nullptr;          // pinned
     hipStream_t stream = nullptr;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    // note events (poly_alloc.hip): the maps live on the device, -1 = none
+    int32_t *d_note2voice = nullptr;   // [128]
+    int32_t *d_voice_note = nullptr;   // [n_pad]
+    void *d_alloc = nullptr;           // the scan's per-workgroup lists
+    // a batch's parsed events (note | on << 8, increment), staged in pinned memory: two slots, so the host fills
+    // one while the copy of the other may still be in flight
+    uint32_t *h_ops[2] = {nullptr, nullptr};
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    bool ev_stage_busy[2] = {false, false};
+    size_t ops_cap = 0;                // events per slot
+    uint32_t *d_ops = nullptr;
+    int ev_k = 0;
 };
 
 static void poly_slots(smx::PolyArrays &d, void **slots[12])
@@ -50,7 +62,12 @@ extern "C" smx_poly *smx_poly_create(uint32_t n_voices, int device)
               hipMemsetAsync(p->d_bus2, 0, 2 * smx::poly_bus_bytes(), p->stream) == hipSuccess &&
               hipMalloc((void **)&p->d_slots, smx::poly_scratch_bytes()) == hipSuccess &&
               hipMemsetAsync(p->d_slots, 0, smx::poly_scratch_bytes(), p->stream) == hipSuccess &&
-              hipHostMalloc((void **)&p->h_bus, 128 * 4, hipHostMallocDefault) == hipSuccess;
+              hipHostMalloc((void **)&p->h_bus, 128 * 4, hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void **)&p->d_note2voice, 128 * 4) == hipSuccess &&
+              hipMalloc((void **)&p->d_voice_note, bytes) == hipSuccess &&
+              hipMemsetAsync(p->d_note2voice, 0xFF, 128 * 4, p->stream) == hipSuccess &&
+              hipMemsetAsync(p->d_voice_note, 0xFF, bytes, p->stream) == hipSuccess &&
+              hipMalloc(&p->d_alloc, smx::poly_alloc_scratch_bytes(n_voices)) == hipSuccess;
     for (int i = 0; ok && i < 12; i++)
         ok = hipMalloc(slots[i], bytes) == hipSuccess &&
              hipMemsetAsync(*slots[i], 0, bytes, p->stream) == hipSuccess;   // inc 0: all voices off
@@ -75,6 +92,14 @@ extern "C" void smx_poly_destroy(smx_poly *p)
     if (p->d_bus2) (void)hipFree(p->d_bus2);
     if (p->d_slots) (void)hipFree(p->d_slots);
     if (p->h_bus) (void)hipHostFree(p->h_bus);
+    if (p->d_note2voice) (void)hipFree(p->d_note2voice);
+    if (p->d_voice_note) (void)hipFree(p->d_voice_note);
+    if (p->d_alloc) (void)hipFree(p->d_alloc);
+    if (p->d_ops) (void)hipFree(p->d_ops);
+    for (int i = 0; i < 2; i++) {
+        if (p->h_ops[i]) (void)hipHostFree(p->h_ops[i]);
+        if (p->ev_stage[i]) (void)hipEventDestroy(p->ev_stage[i]);
+    }
     if (p->ev_t0) (void)hipEventDestroy(p->ev_t0);
     if (p->ev_t1) (void)hipEventDestroy(p->ev_t1);
     if (p->stream) (void)hipStreamDestroy(p->stream);
@@ -94,6 +119,11 @@ static int poly_copy(smx_poly *p, const struct smx_poly_arrays *a, bool to_devic
         if (!host[i]) continue;
         if (to_device) SMX_HIP(hipMemcpy(*slots[i], host[i], (size_t)p->n * 4, hipMemcpyHostToDevice));
         else           SMX_HIP(hipMemcpy(host[i], *slots[i], (size_t)p->n * 4, hipMemcpyDeviceToHost));
+    }
+    if (to_device && (a->inc || a->gate)) {          // new increments or gates: no voice holds a note any more
+        SMX_HIP(hipMemsetAsync(p->d_note2voice, 0xFF, 128 * 4, p->stream));
+        SMX_HIP(hipMemsetAsync(p->d_voice_note, 0xFF, (size_t)p->n_pad * 4, p->stream));
+        SMX_HIP(hipStreamSynchronize(p->stream));
     }
     return SMX_OK;
 }
@@ -159,3 +189,121 @@ extern "C" int smx_poly_timer_stop(smx_poly *p, float *ms)
     return SMX_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// note events: the allocator runs on the device (poly_alloc.hip), in event order, without a host sync
+// ---------------------------------------------------------------------------
+// The staging slot for a batch of up to n events (grown, with a sync, only when a batch is larger than any before).
+static int poly_stage(smx_poly *p, size_t n, uint32_t **ops)
+{
+    if (p->n >= 0x80000000u) { set_error("smx_poly note events: n_voices=%u (< 2^31)", p->n); return SMX_E_RANGE; }
+    SMX_HIP(hipSetDevice(p->device));
+    if (p->ops_cap < n) {
+        SMX_HIP(hipStreamSynchronize(p->stream));
+        size_t cap = p->ops_cap ? p->ops_cap : 1024u;
+        while (cap < n) cap *= 2;
+        for (int i = 0; i < 2; i++) {
+            if (p->h_ops[i]) SMX_HIP(hipHostFree(p->h_ops[i]));
+            p->h_ops[i] = nullptr;
+            SMX_HIP(hipHostMalloc((void **)&p->h_ops[i], cap * 8, hipHostMallocDefault));
+            if (!p->ev_stage[i]) SMX_HIP(hipEventCreateWithFlags(&p->ev_stage[i], hipEventDisableTiming));
+            p->ev_stage_busy[i] = false;
+        }
+        if (p->d_ops) SMX_HIP(hipFree(p->d_ops));
+        p->d_ops = nullptr;
+        SMX_HIP(hipMalloc((void **)&p->d_ops, cap * 8));
+        p->ops_cap = cap;
+    }
+    const int k = p->ev_k;
+    if (p->ev_stage_busy[k]) {                               // the copy that last read this slot
+        SMX_HIP(hipEventSynchronize(p->ev_stage[k]));
+        p->ev_stage_busy[k] = false;
+    }
+    *ops = p->h_ops[k];
+    return SMX_OK;
+}
+
+static inline void put_op(uint32_t *ops, size_t i, bool on, int note)
+{
+    const int m = note % 128;
+    ops[2 * i] = (uint32_t)m | (uint32_t)on << 8;
+    ops[2 * i + 1] = note_to_inc(m);
+}
+
+// The n events staged in the current slot -> one H2D copy, then per POLY_EV_CAP events one launch of the allocator
+// (two kernels when the launch holds a note_on, one otherwise).  Stream order puts them after the blocks queued
+// before and ahead of the next one; the deferred fold of the last block (PolyPending) touches only its bus and
+// copies, never the arrays written here, so it stays owed to the next launch.
+static int poly_submit(smx_poly *p, size_t n)
+{
+    if (n == 0) return SMX_OK;                               // nothing to do: nothing launched
+    const int k = p->ev_k;
+    const uint32_t *ops = p->h_ops[k];
+    SMX_HIP(hipMemcpyAsync(p->d_ops, ops, n * 8, hipMemcpyHostToDevice, p->stream));
+    SMX_HIP(hipEventRecord(p->ev_stage[k], p->stream));
+    p->ev_stage_busy[k] = true;
+    p->ev_k ^= 1;
+    for (size_t e0 = 0; e0 < n; e0 += smx::POLY_EV_CAP) {
+        const uint32_t ne = (uint32_t)(n - e0 < (size_t)smx::POLY_EV_CAP ? n - e0 : (size_t)smx::POLY_EV_CAP);
+        bool any_on = false;
+        for (uint32_t i = 0; i < ne; i++) any_on |= (ops[2 * (e0 + i)] >> 8) != 0;
+        const int rv = smx::launch_poly_alloc(p->d, p->d_note2voice, p->d_voice_note, p->d_ops + 2 * e0, ne, any_on,
+                                              p->n, p->d_alloc, p->stream);
+        if (rv) return rv;
+    }
+    return SMX_OK;
+}
+
+static int poly_note(smx_poly *p, int note, bool on, const char *what)
+{
+    if (!p) { set_error("%s: null bank", what); return SMX_E_ARG; }
+    if (note < 0) { set_error("%s: note %d < 0", what, note); return SMX_E_ARG; }
+    uint32_t *ops;
+    int rv = poly_stage(p, 1, &ops);
+    if (rv) return rv;
+    put_op(ops, 0, on, note);
+    return poly_submit(p, 1);
+}
+
+extern "C" int smx_poly_note_on(smx_poly *p, int note) { return poly_note(p, note, true, "smx_poly_note_on"); }
+extern "C" int smx_poly_note_off(smx_poly *p, int note) { return poly_note(p, note, false, "smx_poly_note_off"); }
+
+// process_midi dispatch (linux/synth.c:236-258) of a 3-byte message: 1 note_on, 0 note_off, -1 ignored
+static int midi_kind(const uint8_t *m)
+{
+    if (m[0] == 0x90) return m[2] != 0 ? 1 : 0;              // velocity 0: note_off
+    if (m[0] == 0x80) return 0;
+    return -1;
+}
+
+extern "C" int smx_poly_midi_event(smx_poly *p, const uint8_t *msg, size_t size)
+{
+    if (!p || (size && !msg)) { set_error("smx_poly_midi_event: bad args"); return SMX_E_ARG; }
+    if (size != 3) return SMX_OK;
+    const int kind = midi_kind(msg);
+    return kind < 0 ? SMX_OK : poly_note(p, msg[1], kind == 1, "smx_poly_midi_event");
+}
+
+extern "C" int smx_poly_midi_events(smx_poly *p, const uint8_t *msgs3, size_t n_events)
+{
+    if (!p || (n_events && !msgs3)) { set_error("smx_poly_midi_events: bad args"); return SMX_E_ARG; }
+    if (n_events == 0) return SMX_OK;
+    uint32_t *ops;
+    int rv = poly_stage(p, n_events, &ops);
+    if (rv) return rv;
+    size_t n = 0;
+    for (size_t i = 0; i < n_events; i++) {
+        const int kind = midi_kind(msgs3 + 3 * i);
+        if (kind >= 0) put_op(ops, n++, kind == 1, msgs3[3 * i + 1]);
+    }
+    return poly_submit(p, n);
+}
+
+extern "C" int smx_poly_read_notes(smx_poly *p, int32_t note2voice[128])
+{
+    if (!p || !note2voice) { set_error("smx_poly_read_notes: bad args"); return SMX_E_ARG; }
+    SMX_HIP(hipSetDevice(p->device));
+    SMX_HIP(hipStreamSynchronize(p->stream));
+    SMX_HIP(hipMemcpy(note2voice, p->d_note2voice, 128 * 4, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}

@@ -137,6 +137,15 @@ size_t poly_bus_bytes();
 int launch_poly_flush(PolyPending *pend, hipStream_t stream);
 int launch_poly_bank(const PolyArrays &p, int32_t *d_bus_lr, int32_t *d_slots, uint32_t n_pad,
                      uint32_t nframes, hipStream_t stream, PolyPending *pend = nullptr);
+// Note events of the poly bank (poly_alloc.hip): at most POLY_EV_CAP events per launch, as pairs
+// (note | on << 8, note_to_inc(note)) in device memory; note2voice[128] / voice_note[n_pad] hold -1 for none.
+// any_on == false (no note_on among them): no pass over the bank.  n < 2^31 (the index is 31 bits of the key).
+// d_scratch: poly_alloc_scratch_bytes(n) bytes (the scan's per-workgroup lists).
+enum { POLY_EV_CAP = 64, POLY_ALLOC_MAX_WG = 128 };
+uint32_t poly_alloc_lists(uint32_t n);
+size_t poly_alloc_scratch_bytes(uint32_t n);
+int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, const uint32_t *d_ops,
+                      uint32_t n_ops, bool any_on, uint32_t n, void *d_scratch, hipStream_t stream);
 
 // Noise-shaped PWM bank (pwm_bank.hip): device SoA arrays, n_pad entries each.
 struct PwmArrays {
