@@ -7,7 +7,7 @@ ARCH    ?= gfx950
 CSRC    := synth_tools_amd/csrc
 OBJDIR  := synth_tools_amd/build
 LIB     := synth_tools_amd/libsynth_mi355x.so
-SRCS    := saw_bank.hip pdm_bank.hip poly_bank.hip pwm_bank.hip osc_bank.hip cproc_bank.hip \
+SRCS    := saw_bank.hip pdm_bank.hip poly_bank.hip poly_alloc.hip pwm_bank.hip osc_bank.hip cproc_bank.hip \
            abi_core.cpp abi_saw.cpp abi_pdm.cpp abi_pwm.cpp abi_poly.cpp abi_osc.cpp abi_cproc.cpp abi_fw.cpp
 OBJS    := $(addprefix $(OBJDIR)/,$(addsuffix .o,$(SRCS)))
 HDRS    := $(CSRC)/smx_common.h $(CSRC)/abi_internal.h include/synth_mi355x.h
