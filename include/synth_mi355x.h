@@ -148,6 +148,12 @@ int smx_bank_set_block_mode(smx_bank *b, int mode);
 int smx_bank_set_block_form(smx_bank *b, int form);
 /* The form the next long block will run (SMX_FORM_STEPPING / SMX_FORM_EVENTS); synchronises. */
 int smx_bank_next_block_form(smx_bank *b);
+/* Note codes: next to the increments a bank of 2^16 voices or more keeps one byte per voice (0 off, 1 + note for
+ * note_to_inc(note), an escape for any other increment); while no voice holds an escape, blocks of 1..4 frames on
+ * 2^20 voices or more read the codes instead of the increments (5 instead of 8 bytes per voice, same bits).
+ * *escapes = the number of voices whose increment has no code.  Synchronises; for tests and tools.
+ * SMX_E_STATE on a bank below 2^16 voices (no codes kept). */
+int smx_bank_code_stats(smx_bank *b, uint32_t *escapes);
 
 /* Asynchronous form: enqueue one block of n frames on the bank's stream and
  * leave the int32 bus in device memory (smx_bank_bus_dev).  No host sync.

@@ -97,6 +97,7 @@ ABI = [
     ("smx_bank_set_block_mode", C.c_int, [_P, C.c_int]),
     ("smx_bank_set_block_form", C.c_int, [_P, C.c_int]),
     ("smx_bank_next_block_form", C.c_int, [_P]),
+    ("smx_bank_code_stats", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("smx_bank_run_async", C.c_int, [_P, C.c_int]),
     ("smx_bank_bus_dev", _P, [_P]),
     ("smx_bank_sync", C.c_int, [_P]),
@@ -281,6 +282,12 @@ class SawBank:
 
     def next_block_form(self):
         return lib().smx_bank_next_block_form(self._h)
+
+    def code_stats(self):
+        """Voices whose increment is not a note code (0: tick blocks read the 1-byte codes).  Synchronises."""
+        e = C.c_uint32()
+        _check(lib().smx_bank_code_stats(self._h, C.byref(e)), "smx_bank_code_stats")
+        return e.value
 
     def midi_event(self, msg):
         m = np.ascontiguousarray(msg, np.uint8)

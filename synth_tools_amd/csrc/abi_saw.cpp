@@ -4,6 +4,7 @@
 #include "abi_internal.h"
 #include <rccl/rccl.h>
 #include <time.h>
+#include <algorithm>
 #include <unordered_map>
 
 #define SMX_NCCL(expr)                                                         \
@@ -107,6 +108,12 @@ struct smx_bank {
     // Blocks only read; the host adds the block length to `elapsed`.
     uint32_t *d_state0 = nullptr;
     bool one_alloc = false;                      // d_state0 lies in d_inc's allocation (the default)
+    // One note code per voice (smx::SawCodeTab, saw_bank.hip's tick kernel) and the code table, right behind
+    // state0[] in state0's allocation -- the one allocation of the bank, or the second one with SMX_BANK_TWO_ALLOCS.
+    // Kept in step with d_inc on banks with a scratch header (n_pad >= 2^16): the load paths re-encode through
+    // launch_saw_sum_inc, the note events through the rebase kernels.
+    uint8_t *d_code = nullptr;
+    smx::SawCodeTab *d_ctab = nullptr;
     uint32_t elapsed = 0;
     // A ring of bus buffers: [cur] holds the last block (and may be feeding an all-reduce),
     // [cur+1] was zeroed by the last launch for the next one, [cur+2] is the one the next
@@ -198,6 +205,33 @@ struct smx_bank {
 
 static int bank_comm_flush(smx_bank *b);
 
+// The note alphabet: code 0 = off, code 1 + note = note_to_inc(note), SAW_CODE_ESC for anything else.
+static const smx::SawCodeTab &saw_code_tab()
+{
+    static const smx::SawCodeTab tab = [] {
+        smx::SawCodeTab t{};
+        uint64_t key[128];                                     // (increment, code), sorted by increment
+        for (int note = 0; note < 128; note++) {
+            t.dec[note + 1] = note_to_inc(note);
+            key[note] = ((uint64_t)t.dec[note + 1] << 32) | (uint32_t)(note + 1);
+        }
+        std::sort(key, key + 128);
+        for (int i = 0; i < 128; i++) {
+            t.enc_inc[i] = (uint32_t)(key[i] >> 32);
+            t.enc_code[i] = (uint32_t)key[i];
+        }
+        return t;
+    }();
+    return tab;
+}
+static uint32_t saw_code_of(uint32_t inc)
+{
+    if (inc == 0) return 0;
+    const smx::SawCodeTab &t = saw_code_tab();
+    const uint32_t *p = std::lower_bound(t.enc_inc, t.enc_inc + 128, inc);
+    return (p != t.enc_inc + 128 && *p == inc) ? t.enc_code[p - t.enc_inc] : smx::SAW_CODE_ESC;
+}
+
 // The increments changed (load / note event): what the host has seen of the device's picks is void.
 static void bank_form_unpin(smx_bank *b)
 {
@@ -273,7 +307,7 @@ static int bank_ensure_bus(smx_bank *b, uint32_t n)
         b->pend = smx::SawPending{};
         b->pend.region_stride = no_defer ? 0 : smx::saw_scratch_region_bytes(scap);
         // a new header: the sum of the increments and the form pick are computed again
-        int rv = smx::launch_saw_sum_inc(b->d_inc, b->n_pad, b->d_scratch, b->stream);
+        int rv = smx::launch_saw_sum_inc(b->d_inc, b->d_code, b->d_ctab, b->n_pad, b->d_scratch, b->stream);
         if (rv) return rv;
         bank_form_unpin(b);
     }
@@ -304,6 +338,7 @@ extern "C" smx_bank *smx_bank_create(uint32_t n_voices, int device)
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return fail("hipSetDevice", e);
     const size_t bytes = (size_t)b->n_pad * 4;
+    const size_t tail = (size_t)b->n_pad + sizeof(smx::SawCodeTab);      // code[n_pad] and the code table behind state0[]
     {
         // Both arrays in ONE allocation, state0[] right behind inc[] (round 3).  The HBM-bound tick step is bimodal by
         // PROCESS with two allocations -- 76 us or 82 us on 64 Mi voices, depending on where the second one lands
@@ -312,13 +347,15 @@ extern "C" smx_bank *smx_bank_create(uint32_t n_voices, int device)
         // 76.2-77.7 with two on the same box (profiles/r03_one_alloc.txt).  SMX_BANK_TWO_ALLOCS=1: as before.
         static const bool two = getenv("SMX_BANK_TWO_ALLOCS") != nullptr;
         if (!two) {
-            if ((e = hipMalloc((void **)&b->d_inc, 2 * bytes)) != hipSuccess) return fail("hipMalloc inc+state", e);
+            if ((e = hipMalloc((void **)&b->d_inc, 2 * bytes + tail)) != hipSuccess) return fail("hipMalloc inc+state", e);
             b->d_state0 = b->d_inc + b->n_pad;
             b->one_alloc = true;
         } else {
             if ((e = hipMalloc((void **)&b->d_inc, bytes)) != hipSuccess) return fail("hipMalloc inc", e);
-            if ((e = hipMalloc((void **)&b->d_state0, bytes)) != hipSuccess) return fail("hipMalloc state", e);
+            if ((e = hipMalloc((void **)&b->d_state0, bytes + tail)) != hipSuccess) return fail("hipMalloc state", e);
         }
+        b->d_code = reinterpret_cast<uint8_t *>(b->d_state0 + b->n_pad);           // n_pad is a multiple of 1024
+        b->d_ctab = reinterpret_cast<smx::SawCodeTab *>(b->d_code + b->n_pad);
     }
     if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess) return fail("stream", e);
     if ((e = hipHostMalloc((void **)&b->h_form, 64, hipHostMallocDefault)) != hipSuccess) return fail("hipHostMalloc", e);
@@ -337,7 +374,9 @@ extern "C" smx_bank *smx_bank_create(uint32_t n_voices, int device)
     }
     // synth_init: bzero (linux/synth.c:204-206); padding voices stay off forever
     if ((e = hipMemsetAsync(b->d_inc, 0, bytes, b->stream)) != hipSuccess) return fail("memset", e);
-    if ((e = hipMemsetAsync(b->d_state0, 0, bytes, b->stream)) != hipSuccess) return fail("memset", e);
+    if ((e = hipMemsetAsync(b->d_state0, 0, bytes + (size_t)b->n_pad, b->stream)) != hipSuccess) return fail("memset", e);   // code 0: off
+    if ((e = hipMemcpyAsync(b->d_ctab, &saw_code_tab(), sizeof(smx::SawCodeTab), hipMemcpyHostToDevice, b->stream)) != hipSuccess)
+        return fail("code table", e);
     if ((e = hipStreamSynchronize(b->stream)) != hipSuccess) return fail("sync", e);
     memset(b->note2voice, 0, sizeof(b->note2voice));
     b->free_map.reset(b->n, true);
@@ -471,7 +510,7 @@ extern "C" int smx_bank_load(smx_bank *b, const uint32_t *inc, const uint32_t *s
         // of the whole bank: launch_saw_sum_inc), what the host has seen of the old bank's picks is void
         if (b->d_scratch) {
             SMX_HIP(hipMemsetAsync(b->d_scratch, 0, smx::saw_scratch_header_bytes(), b->stream));
-            rv = smx::launch_saw_sum_inc(b->d_inc, b->n_pad, b->d_scratch, b->stream);    // the header's sum of increments
+            rv = smx::launch_saw_sum_inc(b->d_inc, b->d_code, b->d_ctab, b->n_pad, b->d_scratch, b->stream);    // the header's sum of increments
             if (rv) return rv;
         }
         bank_form_unpin(b);
@@ -501,7 +540,7 @@ extern "C" int smx_bank_load_run(smx_bank *b, const uint32_t *inc, const uint32_
     if (b->d_scratch) {
         // as in smx_bank_load: the long-block forms take the bank's sum of increments from the scratch header
         SMX_HIP(hipMemsetAsync(b->d_scratch, 0, smx::saw_scratch_header_bytes(), b->stream));
-        int rv = smx::launch_saw_sum_inc(b->d_inc, b->n_pad, b->d_scratch, b->stream);
+        int rv = smx::launch_saw_sum_inc(b->d_inc, b->d_code, b->d_ctab, b->n_pad, b->d_scratch, b->stream);
         if (rv) return rv;
     }
     bank_form_unpin(b);
@@ -533,7 +572,8 @@ static int bank_set_inc(smx_bank *b, uint32_t v, uint32_t inc)
     uint32_t local;
     if (!bank_owns(b, v, &local)) return SMX_OK;
     SMX_HIP(hipSetDevice(b->device));
-    int rv = smx::launch_saw_rebase(b->d_inc, b->d_state0, local, inc, b->elapsed, b->d_scratch, b->n_pad, b->stream);
+    int rv = smx::launch_saw_rebase(b->d_inc, b->d_state0, b->d_code, local, inc, saw_code_of(inc), b->elapsed,
+                                    b->d_scratch, b->n_pad, b->stream);
     if (rv) return rv;
     bank_form_unpin(b);
     return SMX_OK;
@@ -695,7 +735,7 @@ static int bank_run_async(smx_bank *b, int n, const smx::SawPublish *pub, bool *
         if (b->form_stable >= smx_bank::FORM_STABLE && b->form_seen <= 1u)
             form = b->form_seen ? SMX_FORM_EVENTS : SMX_FORM_STEPPING;
     }
-    rv = smx::launch_saw_bank(b->d_inc, b->d_state0, b->d_bus[bi], b->d_bus[bnext], b->n_pad, (uint32_t)n,
+    rv = smx::launch_saw_bank(b->d_inc, b->d_state0, b->d_code, b->d_ctab, b->d_bus[bi], b->d_bus[bnext], b->n_pad, (uint32_t)n,
                               b->elapsed, b->d_scratch, form, b->h_form, b->long_tag, b->stream, &b->pend, pub, published);
     if (rv) return rv;
     b->elapsed += (uint32_t)n;             // mod 2^32, like the phases
@@ -786,7 +826,8 @@ extern "C" int smx_bank_midi_events(smx_bank *b, const uint8_t *msgs3, size_t n_
     b->ev_stage_busy[k] = true;
     b->ev_k ^= 1;
     bank_form_unpin(b);
-    return smx::launch_saw_rebase_batch(b->d_inc, b->d_state0, b->d_ev, npairs, b->elapsed, b->d_scratch, b->n_pad, b->stream);
+    return smx::launch_saw_rebase_batch(b->d_inc, b->d_state0, b->d_code, b->d_ctab, b->d_ev, npairs, b->elapsed,
+                                        b->d_scratch, b->n_pad, b->stream);
 }
 
 extern "C" int smx_bank_sync(smx_bank *b)
@@ -919,6 +960,18 @@ extern "C" int smx_bank_set_block_form(smx_bank *b, int form)
         return SMX_E_ARG;
     }
     b->block_form = form;
+    return SMX_OK;
+}
+
+// How many voices hold an increment outside the note alphabet (0: the tick path reads the 1-byte codes)?
+// Synchronises; for tests and tools.
+extern "C" int smx_bank_code_stats(smx_bank *b, uint32_t *escapes)
+{
+    if (!b || !escapes) { set_error("smx_bank_code_stats: bad args"); return SMX_E_ARG; }
+    if (!b->d_scratch) { set_error("smx_bank_code_stats: a bank of %u voices keeps no codes (from 2^16 voices up)", b->n); return SMX_E_STATE; }
+    SMX_HIP(hipSetDevice(b->device));
+    SMX_HIP(hipStreamSynchronize(b->stream));
+    SMX_HIP(hipMemcpy(escapes, static_cast<uint32_t *>(b->d_scratch) + smx::SAW_HDR_ESCAPES, 4, hipMemcpyDeviceToHost));
     return SMX_OK;
 }
 

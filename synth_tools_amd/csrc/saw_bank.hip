@@ -109,6 +109,9 @@ struct SawPartial {
 //   [4..5] exact sum of all increments: computed when the increments are loaded (saw_sum_inc_kernel), kept
 //          current by the note-event kernels; the finalize kernels take the bank's I from here (the main kernels
 //          do not add the increments up again at every launch).
+//   [6] (smx::SAW_HDR_ESCAPES) number of voices whose increment has no note code (code ESC): counted when the
+//       increments are loaded (saw_sum_inc_kernel), kept current by the note-event kernels (saw_code_note); the
+//       tick kernel reads the 1-byte codes instead of the increments while it is 0.
 // The finalize kernel writes [0] from the launch's own largest increment and the sum of increments.
 // Note events keep it CONSERVATIVE in between: a new increment above the bound, or a running sum above the
 // bound, clears [0] at once (saw_stats_note), so that the event form never runs on a bank the rule would not
@@ -295,38 +298,89 @@ void saw_direct_finalize_kernel(SawPartial *__restrict__ partial, int32_t *__res
 // bus atomic per frame per workgroup; big workgroups give the stream the same bytes in flight
 // with a quarter of the workgroups (256 x 1024 threads: 6.9 TB/s), and a quarter of the
 // serialised atomics.  Partial sums are folded with wave shuffles instead of the LDS matrix.
+//
+// The stream is at the fabric's read ceiling (8 B per voice at 7.0-7.2 TB/s), so the launch reads fewer bytes when
+// it can: when the header counts no escapes (hdr[SAW_HDR_ESCAPES] == 0, decided here on the device, because note
+// events are queued asynchronously), every increment is one of the 129 of the note alphabet and a lane reads its 4
+// voices' one-byte codes (4 B) instead of their increments (16 B): 5 B per voice.  Each workgroup first puts
+// off[c] = tbase * inc(c) and inc(c) for all 256 codes into LDS, so the start phase is state0 + off[c] -- the same
+// integers as state0 + tbase * inc, mod 2^32 -- without a per-voice multiply.  code == nullptr (no codes, or
+// SMX_SAW_NO_CODES=1) or escapes: the 8-byte path.
 template <int TC, bool NT>
 __global__ __launch_bounds__(1024)
 void saw_tick_kernel(const uint32_t *__restrict__ inc, const uint32_t *__restrict__ st_in,
-                     int32_t *__restrict__ bus, int32_t *__restrict__ bus_next,
+                     const uint32_t *__restrict__ code, const smx::SawCodeTab *__restrict__ ctab,
+                     const uint32_t *__restrict__ hdr, int32_t *__restrict__ bus, int32_t *__restrict__ bus_next,
                      uint32_t ngroups, uint32_t nframes, uint32_t tbase)
 {
     __shared__ int32_t W[16][TC];
+    __shared__ uint32_t Loff[256], Linc[TC > 1 ? 256 : 1];
     const uint32_t tid = threadIdx.x;
     if (blockIdx.x == 0 && tid < nframes) bus_next[tid] = 0;     // same contract as saw_bank_kernel
     int32_t acc[TC];
 #pragma unroll
     for (int t = 0; t < TC; t++) acc[t] = 0;
-    const u32x4 *inc4 = reinterpret_cast<const u32x4 *>(inc);
     const u32x4 *st4 = reinterpret_cast<const u32x4 *>(st_in);
     const uint32_t nrows = ngroups >> 10;                        // ngroups is a multiple of 1024 here
-    u32x4 a_next = 0, b_next = 0;
+    // The code table, the first row's phases (both paths read them) and its codes are in flight before the header
+    // word that picks the path is, so that the choice adds no round trip in series (a 1 Mi-voice bank reads from
+    // the caches in ~3.5 us; the 8-byte path then reads one word per lane in vain).
+    uint32_t tab_i = 0, c_next = 0;
+    if (code && tid < 256) tab_i = ctab->dec[tid];
+    u32x4 b_next = 0;
     if (blockIdx.x < nrows) {
-        a_next = stream_load<NT>(inc4 + blockIdx.x * 1024u + tid);
         b_next = stream_load<NT>(st4 + blockIdx.x * 1024u + tid);
+        if (code) c_next = stream_load<NT>(code + blockIdx.x * 1024u + tid);
     }
-    for (uint32_t row = blockIdx.x; row < nrows; row += gridDim.x) {
-        const u32x4 a = a_next, b = b_next;
-        const uint32_t rn = min(row + gridDim.x, nrows - 1) * 1024u + tid;   // software prefetch
-        a_next = stream_load<NT>(inc4 + rn);
-        b_next = stream_load<NT>(st4 + rn);
-        u32x4 s = b + tbase * a;
-        // an inactive voice (inc == 0) contributes nothing: park it at 0
-        s.x = a.x ? s.x : 0u; s.y = a.y ? s.y : 0u; s.z = a.z ? s.z : 0u; s.w = a.w ? s.w : 0u;
+    // (uniform over the workgroup: the same header word for every lane)
+    const bool coded = code && __builtin_amdgcn_readfirstlane(hdr[smx::SAW_HDR_ESCAPES]) == 0u;
+    if (coded) {
+        if (tid < 256) {
+            Loff[tid] = tbase * tab_i;
+            if constexpr (TC > 1) Linc[tid] = tab_i;
+        }
+        __syncthreads();
+        for (uint32_t row = blockIdx.x; row < nrows; row += gridDim.x) {
+            const uint32_t c = c_next;
+            const u32x4 b = b_next;
+            const uint32_t rn = min(row + gridDim.x, nrows - 1) * 1024u + tid;   // software prefetch
+            c_next = stream_load<NT>(code + rn);
+            b_next = stream_load<NT>(st4 + rn);
+            const uint32_t c0 = c & 255u, c1 = (c >> 8) & 255u, c2 = (c >> 16) & 255u, c3 = c >> 24;
+            // an inactive voice (code 0) contributes nothing: park it at 0 (a mask, not a select: the compiler
+            // would otherwise branch around each table read; every code indexes the 256-entry table)
+            u32x4 s;
+            s.x = (b.x + Loff[c0]) & (0u - (uint32_t)(c0 != 0u)); s.y = (b.y + Loff[c1]) & (0u - (uint32_t)(c1 != 0u));
+            s.z = (b.z + Loff[c2]) & (0u - (uint32_t)(c2 != 0u)); s.w = (b.w + Loff[c3]) & (0u - (uint32_t)(c3 != 0u));
+            if constexpr (TC == 1) {
+                acc_add4<false>(acc[0], (int32_t)s.x >> 4, (int32_t)s.y >> 4, (int32_t)s.z >> 4, (int32_t)s.w >> 4);
+            } else {
+                u32x4 a;
+                a.x = Linc[c0]; a.y = Linc[c1]; a.z = Linc[c2]; a.w = Linc[c3];
 #pragma unroll
-        for (int t = 0; t < TC; t++) {
-            acc_add4<false>(acc[t], (int32_t)s.x >> 4, (int32_t)s.y >> 4, (int32_t)s.z >> 4, (int32_t)s.w >> 4);
-            s += a;
+                for (int t = 0; t < TC; t++) {
+                    acc_add4<false>(acc[t], (int32_t)s.x >> 4, (int32_t)s.y >> 4, (int32_t)s.z >> 4, (int32_t)s.w >> 4);
+                    s += a;
+                }
+            }
+        }
+    } else {
+        const u32x4 *inc4 = reinterpret_cast<const u32x4 *>(inc);
+        u32x4 a_next = 0;
+        if (blockIdx.x < nrows) a_next = stream_load<NT>(inc4 + blockIdx.x * 1024u + tid);
+        for (uint32_t row = blockIdx.x; row < nrows; row += gridDim.x) {
+            const u32x4 a = a_next, b = b_next;
+            const uint32_t rn = min(row + gridDim.x, nrows - 1) * 1024u + tid;   // software prefetch
+            a_next = stream_load<NT>(inc4 + rn);
+            b_next = stream_load<NT>(st4 + rn);
+            u32x4 s = b + tbase * a;
+            // an inactive voice (inc == 0) contributes nothing: park it at 0
+            s.x = a.x ? s.x : 0u; s.y = a.y ? s.y : 0u; s.z = a.z ? s.z : 0u; s.w = a.w ? s.w : 0u;
+#pragma unroll
+            for (int t = 0; t < TC; t++) {
+                acc_add4<false>(acc[t], (int32_t)s.x >> 4, (int32_t)s.y >> 4, (int32_t)s.z >> 4, (int32_t)s.w >> 4);
+                s += a;
+            }
         }
     }
 #pragma unroll
@@ -815,6 +869,27 @@ __device__ __forceinline__ void saw_stats_note(uint32_t *__restrict__ hdr, uint3
     if (s > ((unsigned long long)nvoices << 27)) hdr[0] = 0u;
 }
 
+// The code of an increment (smx::SawCodeTab): 0 for off, the note's code, or ESC.  enc_inc: the 128 note increments
+// sorted ascending (branchless lower bound, 7 probes, every index within 0..127).
+__device__ __forceinline__ uint32_t saw_encode(const uint32_t *enc_inc, const uint32_t *enc_code, uint32_t i)
+{
+    if (i == 0) return 0u;
+    uint32_t lo = 0;
+#pragma unroll
+    for (uint32_t step = 64; step; step >>= 1)
+        if (enc_inc[lo + step - 1] < i) lo += step;
+    return enc_inc[lo] == i ? enc_code[lo] : smx::SAW_CODE_ESC;
+}
+// A note event writes one voice's code: keep the header's escape count (down as well as up).
+__device__ __forceinline__ void saw_code_note(uint32_t *__restrict__ hdr, uint8_t *__restrict__ code, uint32_t voice,
+                                              uint32_t new_code)
+{
+    const uint32_t old_code = code[voice];
+    code[voice] = (uint8_t)new_code;
+    const int d = (int)(new_code == smx::SAW_CODE_ESC) - (int)(old_code == smx::SAW_CODE_ESC);
+    if (d) atomicAdd(hdr + smx::SAW_HDR_ESCAPES, (uint32_t)d);
+}
+
 // Finalize of a TL-frame chunk of the long event form (called from saw_bank_finalize_kernel):
 // thread tid owns the frames FPT*tid .. FPT*tid + FPT-1 of the chunk.
 template <uint32_t TL>
@@ -1026,15 +1101,19 @@ void square_bank_kernel(const uint32_t *__restrict__ inc,
 
 // Lazy state maintenance (see the header comment).
 // A note event on one voice at elapsed time T: keep state0 + T*inc continuous.
-__global__ void saw_rebase_kernel(uint32_t *__restrict__ inc, uint32_t *__restrict__ state0,
-                                  uint32_t voice, uint32_t new_inc, uint32_t tbase,
+// (new_code: the code of new_inc, looked up by the host)
+__global__ void saw_rebase_kernel(uint32_t *__restrict__ inc, uint32_t *__restrict__ state0, uint8_t *__restrict__ code,
+                                  uint32_t voice, uint32_t new_inc, uint32_t new_code, uint32_t tbase,
                                   uint32_t *__restrict__ hdr, uint32_t nvoices)     // hdr: scratch header or NULL
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         const uint32_t old = inc[voice];
         state0[voice] += tbase * (old - new_inc);
         inc[voice] = new_inc;
-        if (hdr) saw_stats_note(hdr, nvoices, old, new_inc);
+        if (hdr) {
+            saw_stats_note(hdr, nvoices, old, new_inc);
+            saw_code_note(hdr, code, voice, new_code);
+        }
     }
 }
 // A block's worth of note events at once: pairs[2k] = voice, pairs[2k+1] = its increment after the
@@ -1042,39 +1121,59 @@ __global__ void saw_rebase_kernel(uint32_t *__restrict__ inc, uint32_t *__restri
 // pair per voice: rebasing is linear in inc and all events of a batch share T, so only the final
 // increment matters).  Voices are distinct, one lane per pair.
 __global__ __launch_bounds__(256)
-void saw_rebase_batch_kernel(uint32_t *__restrict__ inc, uint32_t *__restrict__ state0,
-                             const uint32_t *__restrict__ pairs, uint32_t npairs, uint32_t tbase,
-                             uint32_t *__restrict__ hdr, uint32_t nvoices)
+void saw_rebase_batch_kernel(uint32_t *__restrict__ inc, uint32_t *__restrict__ state0, uint8_t *__restrict__ code,
+                             const smx::SawCodeTab *__restrict__ ctab, const uint32_t *__restrict__ pairs,
+                             uint32_t npairs, uint32_t tbase, uint32_t *__restrict__ hdr, uint32_t nvoices)
 {
+    __shared__ uint32_t enc[256];                                 // enc_inc[128], enc_code[128]
+    if (hdr) {
+        enc[threadIdx.x] = threadIdx.x < 128 ? ctab->enc_inc[threadIdx.x] : ctab->enc_code[threadIdx.x - 128];
+        __syncthreads();
+    }
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= npairs) return;
     const uint32_t voice = pairs[2 * k], new_inc = pairs[2 * k + 1];
     const uint32_t old = inc[voice];
     state0[voice] += tbase * (old - new_inc);
     inc[voice] = new_inc;
-    if (hdr) saw_stats_note(hdr, nvoices, old, new_inc);
+    if (hdr) {
+        saw_stats_note(hdr, nvoices, old, new_inc);
+        saw_code_note(hdr, code, voice, saw_encode(enc, enc + 128, new_inc));
+    }
 }
 // I = sum of all increments, into the scratch header (after the increments were loaded; the header was cleared),
 // and their maximum into word [3]: saw_stats_init_kernel, queued behind this one, turns both into the form pick of
 // the bank's first long block (round 3: the pick used to start at "stepping" and only a long block's finalize set it).
+// The same pass writes every voice's note code (four per uint32 word of code4) and counts the escapes into word
+// [SAW_HDR_ESCAPES].
 __global__ __launch_bounds__(256)
-void saw_sum_inc_kernel(const uint32_t *__restrict__ inc, uint32_t n_pad, uint32_t *__restrict__ hdr)
+void saw_sum_inc_kernel(const uint32_t *__restrict__ inc, uint32_t *__restrict__ code4,
+                        const smx::SawCodeTab *__restrict__ ctab, uint32_t n_pad, uint32_t *__restrict__ hdr)
 {
+    __shared__ uint32_t enc[256];                                 // enc_inc[128], enc_code[128]
+    enc[threadIdx.x] = threadIdx.x < 128 ? ctab->enc_inc[threadIdx.x] : ctab->enc_code[threadIdx.x - 128];
+    __syncthreads();
     unsigned long long s = 0;
-    uint32_t mx = 0;
+    uint32_t mx = 0, esc = 0;
     const u32x4 *inc4 = reinterpret_cast<const u32x4 *>(inc);          // n_pad is a multiple of 1024
     for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < n_pad / 4; g += gridDim.x * 256u) {
         const u32x4 a = inc4[g];
         s += (unsigned long long)a.x + a.y + a.z + a.w;
         mx = max(max(mx, a.x), max(max(a.y, a.z), a.w));
+        const uint32_t c0 = saw_encode(enc, enc + 128, a.x), c1 = saw_encode(enc, enc + 128, a.y);
+        const uint32_t c2 = saw_encode(enc, enc + 128, a.z), c3 = saw_encode(enc, enc + 128, a.w);
+        code4[g] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+        esc += (c0 == smx::SAW_CODE_ESC) + (c1 == smx::SAW_CODE_ESC) + (c2 == smx::SAW_CODE_ESC) + (c3 == smx::SAW_CODE_ESC);
     }
     for (int o = 32; o > 0; o >>= 1) {
         s += __shfl_xor(s, o);
         mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+        esc += __shfl_xor(esc, o);
     }
     if ((threadIdx.x & 63) == 0) {
         if (s) atomicAdd(reinterpret_cast<unsigned long long *>(hdr + 4), s);
         if (mx) atomicMax(hdr + 3, mx);
+        if (esc) atomicAdd(hdr + smx::SAW_HDR_ESCAPES, esc);
     }
 }
 // The rule of saw_bank_finalize_kernel on the loaded increments (exact: sum and maximum of the whole bank).
@@ -1264,7 +1363,8 @@ int launch_saw_flush(SawPending *pend, hipStream_t stream, const SawPublish *pub
     return flush_pending(pend, stream, pub, published);
 }
 
-int launch_saw_bank(const uint32_t *d_inc, const uint32_t *d_state_in, int32_t *d_bus,
+int launch_saw_bank(const uint32_t *d_inc, const uint32_t *d_state_in, const uint8_t *d_code, const SawCodeTab *d_ctab,
+                    int32_t *d_bus,
                     int32_t *d_bus_next, uint32_t n_pad, uint32_t nframes, uint32_t tbase,
                     void *d_scratch, int long_block_form, uint32_t *host_flag, uint32_t host_tag,
                     hipStream_t stream, SawPending *pend, const SawPublish *pub, bool *published)
@@ -1438,9 +1538,14 @@ int launch_saw_bank(const uint32_t *d_inc, const uint32_t *d_state_in, int32_t *
             const int rv = flush_pending(pend, stream);
             if (rv) return rv;
         }
-#define SMX_TICK_LAUNCH(TC_, NT_)                                                              \
-    hipLaunchKernelGGL((saw_tick_kernel<TC_, NT_>), dim3(gx), dim3(1024), 0, stream, d_inc,    \
-                       d_state_in, d_bus, d_bus_next, ngroups, nframes, tbase)
+        // the coded path needs the codes and the header that counts their escapes (SMX_SAW_NO_CODES=1: 8-B path)
+        static const bool no_codes = getenv("SMX_SAW_NO_CODES") != nullptr;          // A/B switch
+        const uint32_t *code4 = (no_codes || !d_scratch || !d_code || !d_ctab) ? nullptr
+                                                                               : reinterpret_cast<const uint32_t *>(d_code);
+        const uint32_t *hdr = static_cast<const uint32_t *>(d_scratch);
+#define SMX_TICK_LAUNCH(TC_, NT_)                                                                 \
+    hipLaunchKernelGGL((saw_tick_kernel<TC_, NT_>), dim3(gx), dim3(1024), 0, stream, d_inc,       \
+                       d_state_in, code4, d_ctab, hdr, d_bus, d_bus_next, ngroups, nframes, tbase)
         if (nframes == 1)      { if (nt) SMX_TICK_LAUNCH(1, true); else SMX_TICK_LAUNCH(1, false); }
         else if (nframes == 2) { if (nt) SMX_TICK_LAUNCH(2, true); else SMX_TICK_LAUNCH(2, false); }
         else                   { if (nt) SMX_TICK_LAUNCH(4, true); else SMX_TICK_LAUNCH(4, false); }
@@ -1493,31 +1598,34 @@ int launch_square_bank(const uint32_t *d_inc, const uint32_t *d_state_in, uint32
     return SMX_OK;
 }
 
-int launch_saw_rebase(uint32_t *d_inc, uint32_t *d_state0, uint32_t voice, uint32_t new_inc,
-                      uint32_t tbase, void *d_scratch, uint32_t n_pad, hipStream_t stream)
+int launch_saw_rebase(uint32_t *d_inc, uint32_t *d_state0, uint8_t *d_code, uint32_t voice, uint32_t new_inc,
+                      uint32_t new_code, uint32_t tbase, void *d_scratch, uint32_t n_pad, hipStream_t stream)
 {
-    hipLaunchKernelGGL(saw_rebase_kernel, dim3(1), dim3(64), 0, stream, d_inc, d_state0, voice, new_inc, tbase,
-                       static_cast<uint32_t *>(d_scratch), n_pad);
+    hipLaunchKernelGGL(saw_rebase_kernel, dim3(1), dim3(64), 0, stream, d_inc, d_state0, d_code, voice, new_inc,
+                       new_code, tbase, static_cast<uint32_t *>(d_scratch), n_pad);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }
 
-int launch_saw_rebase_batch(uint32_t *d_inc, uint32_t *d_state0, const uint32_t *d_pairs, uint32_t npairs,
-                            uint32_t tbase, void *d_scratch, uint32_t n_pad, hipStream_t stream)
+int launch_saw_rebase_batch(uint32_t *d_inc, uint32_t *d_state0, uint8_t *d_code, const SawCodeTab *d_ctab,
+                            const uint32_t *d_pairs, uint32_t npairs, uint32_t tbase, void *d_scratch, uint32_t n_pad,
+                            hipStream_t stream)
 {
     if (npairs == 0) return SMX_OK;
     hipLaunchKernelGGL(saw_rebase_batch_kernel, dim3((npairs + 255) / 256), dim3(256), 0, stream, d_inc,
-                       d_state0, d_pairs, npairs, tbase, static_cast<uint32_t *>(d_scratch), n_pad);
+                       d_state0, d_code, d_ctab, d_pairs, npairs, tbase, static_cast<uint32_t *>(d_scratch), n_pad);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }
 
-int launch_saw_sum_inc(const uint32_t *d_inc, uint32_t n_pad, void *d_scratch, hipStream_t stream)
+int launch_saw_sum_inc(const uint32_t *d_inc, uint8_t *d_code, const SawCodeTab *d_ctab, uint32_t n_pad, void *d_scratch,
+                       hipStream_t stream)
 {
     if (!d_scratch) return SMX_OK;
     uint32_t gx = n_pad / 1024;
     if (gx > 2048) gx = 2048;
-    hipLaunchKernelGGL(saw_sum_inc_kernel, dim3(gx), dim3(256), 0, stream, d_inc, n_pad, static_cast<uint32_t *>(d_scratch));
+    hipLaunchKernelGGL(saw_sum_inc_kernel, dim3(gx), dim3(256), 0, stream, d_inc, reinterpret_cast<uint32_t *>(d_code),
+                       d_ctab, n_pad, static_cast<uint32_t *>(d_scratch));
     hipLaunchKernelGGL(saw_stats_init_kernel, dim3(1), dim3(64), 0, stream, static_cast<uint32_t *>(d_scratch), n_pad);
     SMX_HIP(hipGetLastError());
     return SMX_OK;

@@ -75,10 +75,26 @@ int launch_saw_publish(const int32_t *d_bus, int32_t *d_hbus, uint32_t *d_hflag,
 // arguments, the bus goes straight to pinned host memory (published as above).  Nothing in HBM is read or written.
 int launch_saw_dropin(const uint32_t inc[64], const uint32_t state[64], int32_t *d_hbus, uint32_t *d_hflag, uint32_t n,
                       uint32_t seq, hipStream_t stream);
+// Note codes (saw_bank.hip, the coded tick path): next to inc[] the bank keeps one byte per voice, code[v] = 0 for
+// inc == 0, 1 + note for inc == note_to_inc(note), SAW_CODE_ESC for any other increment, and the number of ESC voices
+// in scratch header word SAW_HDR_ESCAPES.  inc[] stays authoritative; the codes are kept in step by every writer of
+// inc[] on banks with a scratch header (launch_saw_sum_inc after a load, the rebase kernels for note events).
+constexpr uint32_t SAW_CODE_ESC = 255;
+constexpr uint32_t SAW_HDR_ESCAPES = 6;          // uint32 word of the scratch header
+// The 129-entry alphabet as the device reads it (one copy per bank, in the bank's allocation behind code[]):
+// dec[c] = the increment of code c (0 for off and for the unused codes 129..255), and the 128 note increments sorted
+// ascending with their codes for the encoders' binary search.
+struct SawCodeTab {
+    uint32_t dec[256];
+    uint32_t enc_inc[128];
+    uint32_t enc_code[128];
+};
 // long_block_form: SMX_FORM_AUTO / SMX_FORM_STEPPING / SMX_FORM_EVENTS (include/synth_mi355x.h)
 // host_flag: two pinned (device-visible) words that receive, after every long block, the form the device
 // would pick next (0 stepping, 1 events) and host_tag, the caller's own number of this block; or NULL.
-int launch_saw_bank(const uint32_t *d_inc, const uint32_t *d_state0, int32_t *d_bus,
+// d_code / d_ctab: the bank's note codes and their table (or NULL: the tick path always reads inc[])
+int launch_saw_bank(const uint32_t *d_inc, const uint32_t *d_state0, const uint8_t *d_code, const SawCodeTab *d_ctab,
+                    int32_t *d_bus,
                     int32_t *d_bus_next, uint32_t n_pad, uint32_t nframes, uint32_t tbase,
                     void *d_scratch, int long_block_form, uint32_t *host_flag, uint32_t host_tag,
                     hipStream_t stream, SawPending *pend = nullptr,       // pend == nullptr: every launch folds its own slots
@@ -86,16 +102,21 @@ int launch_saw_bank(const uint32_t *d_inc, const uint32_t *d_state0, int32_t *d_
 // leading bytes of the scratch area that hold the formulation flag (zero: stepping form) and the bank's sum of
 // increments; after clearing them (new increments) launch_saw_sum_inc recomputes the sum
 size_t saw_scratch_header_bytes();
-int launch_saw_sum_inc(const uint32_t *d_inc, uint32_t n_pad, void *d_scratch, hipStream_t stream);
+// ... and, with it, encodes every increment into d_code and counts the escapes into the (cleared) header
+int launch_saw_sum_inc(const uint32_t *d_inc, uint8_t *d_code, const SawCodeTab *d_ctab, uint32_t n_pad, void *d_scratch,
+                       hipStream_t stream);
 int launch_square_bank(const uint32_t *d_inc, const uint32_t *d_state0, uint32_t *d_or_bus,
                        uint32_t n_pad, uint32_t nframes, uint32_t tbase, hipStream_t stream);
 // one voice's increment changes at elapsed time tbase; state0 += tbase*inc for all voices
 // (d_scratch: the bank's scratch area or NULL -- its header's form pick is kept conservative under note events)
-int launch_saw_rebase(uint32_t *d_inc, uint32_t *d_state0, uint32_t voice, uint32_t new_inc,
-                      uint32_t tbase, void *d_scratch, uint32_t n_pad, hipStream_t stream);
+// (with a scratch header it also writes the voice's code, new_code, and keeps the escape count)
+int launch_saw_rebase(uint32_t *d_inc, uint32_t *d_state0, uint8_t *d_code, uint32_t voice, uint32_t new_inc,
+                      uint32_t new_code, uint32_t tbase, void *d_scratch, uint32_t n_pad, hipStream_t stream);
 // npairs (voice, final increment) pairs with distinct voices, in device memory
-int launch_saw_rebase_batch(uint32_t *d_inc, uint32_t *d_state0, const uint32_t *d_pairs, uint32_t npairs,
-                            uint32_t tbase, void *d_scratch, uint32_t n_pad, hipStream_t stream);
+// (the codes of the new increments are looked up on the device in d_ctab)
+int launch_saw_rebase_batch(uint32_t *d_inc, uint32_t *d_state0, uint8_t *d_code, const SawCodeTab *d_ctab,
+                            const uint32_t *d_pairs, uint32_t npairs, uint32_t tbase, void *d_scratch, uint32_t n_pad,
+                            hipStream_t stream);
 int launch_saw_materialize(const uint32_t *d_inc, uint32_t *d_state0, uint32_t n_pad, uint32_t tbase,
                            hipStream_t stream);
 // Carry-out PDM bank (pdm_bank.hip).  n_pad multiple of 1024; d_bits rows are n_pad/8 bytes.
