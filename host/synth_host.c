@@ -33,6 +33,11 @@
  *                                                rate, pan_l | pan_r << 16; default
  *                                                "0.25,0x00800000,0x00040000,0xA0000000,0x00020000,0x00800080").
  *                                                Not with SYNTH_RANKS.
+ *   SYNTH_POLY_CONTROLLERS=1 SYNTH_POLY=...      the poly bank also honours channel 0's sustain pedal (CC 64), all
+ *                                                sound off (CC 120), reset all controllers (CC 121), all notes off
+ *                                                (CC 123) and pitch bend (smx_poly_set_controllers; DESIGN.md
+ *                                                §3.5c).  SYNTH_POLY_BEND_RANGE=n: bend range in semitones, 0..24
+ *                                                (default 2).  Without them: note on/off only.
  *   SYNTH_FAKE_PERIOD_US=1333 ... --fake-jack    pace the scripted callbacks like a sound card
  *   synth.dynamic.host.elf --fake-jack NBLOCKS NFRAMES EVENTS.bin OUT.f32
  *       EVENTS.bin: records {u32 block; u8 size; u8 bytes[3]} delivered to
@@ -233,6 +238,9 @@ static void setup_poly(uint32_t voices) {
     struct smx_poly_arrays arr = { 0 };
     arr.a = af; arr.ar = u[0]; arr.dr = u[1]; arr.sl = u[2]; arr.rr = u[3]; arr.pan = u[4];
     ASSERT(0 == smx_poly_load(poly, &arr));         /* the rest of the state is zero: silent, idle */
+    const char *ctl = getenv("SYNTH_POLY_CONTROLLERS"), *range = getenv("SYNTH_POLY_BEND_RANGE");
+    if (ctl && atoi(ctl)) ASSERT(0 == smx_poly_set_controllers(poly, 1));
+    if (range) ASSERT(0 == smx_poly_set_bend_range(poly, atoi(range)));
     free(af);
     for (int i = 0; i < 5; i++) free(u[i]);
 }

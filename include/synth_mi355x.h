@@ -324,6 +324,32 @@ int smx_poly_midi_event (smx_poly *p, const uint8_t *msg, size_t size);
 int smx_poly_midi_events(smx_poly *p, const uint8_t *msgs3, size_t n_events);  /* n 3-byte msgs */
 int smx_poly_read_notes(smx_poly *p, int32_t note2voice[128]);                 /* -1 = none; syncs */
 
+/* Controllers of the poly bank, opt-in per bank.  Off (the default): exactly
+ * the dispatch above.  On: channel 0's 3-byte 0xB0 / 0xE0 messages below are honoured too, one at
+ * a time and in order with the notes, ahead of the next block; all else stays ignored.
+ *   CC 64, sustain: value >= 64 pedal down, < 64 up; a repeated value is a no-op.  The bank keeps
+ *     sustained[128].  note_off(m) under a down pedal with note2voice[m] set: sustained[m] = 1,
+ *     gate stays 1, both maps kept.  note_on(m) releases a sustained m as rule 1 (a real
+ *     note_off) and clears sustained[m].  A steal of a voice holding note k clears sustained[k].
+ *     Pedal up: note_off(m) of every sustained m, ascending, bits cleared.
+ *   CC 123, all notes off (any value): note_off of every mapped note, ascending (under a down
+ *     pedal: sustains them).
+ *   CC 120, all sound off (any value): every voice gate = 0, stage = idle, level = 0; both maps
+ *     and sustained cleared; inc, phase, y and the patch untouched; the pedal state is kept.
+ *   CC 121, reset all controllers: pedal up (with its releases), then bend to centre.
+ *   0xE0 lsb msb, pitch bend: b = lsb | msb << 7 (centre 8192).  From the next block on every
+ *     voice's phase advances by (uint32_t)(((uint64_t)inc * mul) >> 16), mul =
+ *     smx_poly_bend_mul(b, range); inc itself (smx_poly_read, the allocator) is not changed, and
+ *     a voice bent to 0 is frozen as inc 0 is.  Bend and range persist across blocks and loads.
+ * smx_poly_load with a non-NULL inc or gate also clears sustained.  Pedal and bend are kept when
+ * the controllers are turned off; a note_off honours the pedal only while they are on.
+ * smx_poly_bend_mul = round(65536 * 2^(range * (b - 8192) / (8192 * 12))), b clamped to
+ * 0..16383 and range to 0..24; exactly 65536 at b = 8192 or range 0. */
+int smx_poly_set_controllers(smx_poly *p, int on);
+int smx_poly_set_bend_range(smx_poly *p, int semitones);          /* 0..24, default 2; SMX_E_ARG outside */
+uint32_t smx_poly_bend_mul(int bend14, int semitones);            /* Q16 increment multiplier */
+int smx_poly_read_sustain(smx_poly *p, uint8_t sustained[128]);   /* 1 = note held by the pedal; syncs */
+
 /* ======================================================================== */
 /* 5. Noise-shaped PWM bank: stm32f103/mod_pdm_pwm.c:76-160, pdm.h:10-77,    */
 /*    mod_controlrate.c:28-57                                                */

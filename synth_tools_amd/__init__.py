@@ -144,6 +144,10 @@ ABI = [
     ("smx_poly_midi_event", C.c_int, [_P, _P, C.c_size_t]),
     ("smx_poly_midi_events", C.c_int, [_P, _P, C.c_size_t]),
     ("smx_poly_read_notes", C.c_int, [_P, _P]),
+    ("smx_poly_set_controllers", C.c_int, [_P, C.c_int]),
+    ("smx_poly_set_bend_range", C.c_int, [_P, C.c_int]),
+    ("smx_poly_bend_mul", C.c_uint32, [C.c_int, C.c_int]),
+    ("smx_poly_read_sustain", C.c_int, [_P, _P]),
     ("smx_pwm_create", _P, [C.c_uint32, C.c_int, C.c_int]),
     ("smx_pwm_destroy", None, [_P]),
     ("smx_pwm_config", C.c_int, [_P, C.c_uint32, C.c_uint32]),
@@ -517,6 +521,25 @@ class PolyBank:
         out = np.empty(128, np.int32)
         _check(lib().smx_poly_read_notes(self._h, _ptr(out)), "smx_poly_read_notes")
         return out
+
+    def set_controllers(self, on):
+        """Honour CC 64/120/121/123 and pitch bend on channel 0 (off by default)."""
+        _check(lib().smx_poly_set_controllers(self._h, 1 if on else 0), "smx_poly_set_controllers")
+
+    def set_bend_range(self, semitones):
+        """Pitch-bend range in semitones, 0..24 (default 2)."""
+        _check(lib().smx_poly_set_bend_range(self._h, int(semitones)), "smx_poly_set_bend_range")
+
+    def read_sustain(self):
+        """-> sustained uint8[128], 1 = note held by the pedal (syncs)"""
+        out = np.empty(128, np.uint8)
+        _check(lib().smx_poly_read_sustain(self._h, _ptr(out)), "smx_poly_read_sustain")
+        return out
+
+
+def poly_bend_mul(b, semitones):
+    """Q16 increment multiplier of pitch bend b (0..16383, centre 8192) at a range of `semitones`."""
+    return int(lib().smx_poly_bend_mul(int(b), int(semitones)))
 
 
 PWM_FIELDS = ("setpoint", "pos0", "vel0", "pos1", "vel1", "s1", "s2", "s3", "s4")

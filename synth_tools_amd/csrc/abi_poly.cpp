@@ -2,6 +2,7 @@
 // Host side of the drop-in boundary.  No CPU compute fallback exists: every compute entry
 // point needs a HIP device and fails with SMX_E_NOGPU otherwise.
 #include "abi_internal.h"
+#include <cmath>
 // ---------------------------------------------------------------------------
 // poly voice bank (build-defined extension; BASELINE config 4)
 // ---------------------------------------------------------------------------
@@ -21,7 +22,14 @@ struct smx_poly {
     int32_t *d_note2voice = nullptr;   // [128]
     int32_t *d_voice_note = nullptr;   // [n_pad]
     void *d_alloc = nullptr;           // the scan's per-workgroup lists
-    // a batch's parsed events (note | on << 8, increment), staged in pinned memory: two slots, so the host fills
+    uint8_t *d_sustained = nullptr;    // [128], 1: the note is held by the pedal
+    // controllers: the pedal and the bend are functions of the event stream alone, so the host
+    // tracks them; only the sustained bits live on the device
+    bool controllers = false;
+    bool pedal = false;
+    int bend14 = 8192, bend_range = 2;
+    uint32_t bend_mul = 65536u;        // passed to every render launch
+    // a batch's parsed events (note | kind << 8, increment), staged in pinned memory: two slots, so the host fills
     // one while the copy of the other may still be in flight
     uint32_t *h_ops[2] = {nullptr, nullptr};
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
@@ -67,7 +75,9 @@ extern "C" smx_poly *smx_poly_create(uint32_t n_voices, int device)
               hipMalloc((void **)&p->d_voice_note, bytes) == hipSuccess &&
               hipMemsetAsync(p->d_note2voice, 0xFF, 128 * 4, p->stream) == hipSuccess &&
               hipMemsetAsync(p->d_voice_note, 0xFF, bytes, p->stream) == hipSuccess &&
-              hipMalloc(&p->d_alloc, smx::poly_alloc_scratch_bytes(n_voices)) == hipSuccess;
+              hipMalloc(&p->d_alloc, smx::poly_alloc_scratch_bytes(n_voices)) == hipSuccess &&
+              hipMalloc((void **)&p->d_sustained, 128) == hipSuccess &&
+              hipMemsetAsync(p->d_sustained, 0, 128, p->stream) == hipSuccess;
     for (int i = 0; ok && i < 12; i++)
         ok = hipMalloc(slots[i], bytes) == hipSuccess &&
              hipMemsetAsync(*slots[i], 0, bytes, p->stream) == hipSuccess;   // inc 0: all voices off
@@ -95,6 +105,7 @@ extern "C" void smx_poly_destroy(smx_poly *p)
     if (p->d_note2voice) (void)hipFree(p->d_note2voice);
     if (p->d_voice_note) (void)hipFree(p->d_voice_note);
     if (p->d_alloc) (void)hipFree(p->d_alloc);
+    if (p->d_sustained) (void)hipFree(p->d_sustained);
     if (p->d_ops) (void)hipFree(p->d_ops);
     for (int i = 0; i < 2; i++) {
         if (p->h_ops[i]) (void)hipHostFree(p->h_ops[i]);
@@ -122,6 +133,7 @@ static int poly_copy(smx_poly *p, const struct smx_poly_arrays *a, bool to_devic
     }
     if (to_device && (a->inc || a->gate)) {          // new increments or gates: no voice holds a note any more
         SMX_HIP(hipMemsetAsync(p->d_note2voice, 0xFF, 128 * 4, p->stream));
+        SMX_HIP(hipMemsetAsync(p->d_sustained, 0, 128, p->stream));
         SMX_HIP(hipMemsetAsync(p->d_voice_note, 0xFF, (size_t)p->n_pad * 4, p->stream));
         SMX_HIP(hipStreamSynchronize(p->stream));
     }
@@ -137,7 +149,8 @@ extern "C" int smx_poly_run_async(smx_poly *p, int n)
     SMX_HIP(hipSetDevice(p->device));
     static const bool no_defer = getenv("SMX_POLY_NO_DEFER") != nullptr;      // A/B switch: every launch folds its own copies
     p->d_bus = p->d_bus2 + (size_t)(p->bus_k++ & 1u) * (smx::poly_bus_bytes() / 4);
-    return smx::launch_poly_bank(p->d, p->d_bus, p->d_slots, p->n_pad, (uint32_t)n, p->stream, no_defer ? nullptr : &p->pend);
+    return smx::launch_poly_bank(p->d, p->d_bus, p->d_slots, p->n_pad, (uint32_t)n, p->stream,
+                                 no_defer ? nullptr : &p->pend, p->bend_mul);
 }
 
 // Whoever is about to read the last block's bus first runs the fold its launch deferred (a no-op when nothing is owed).
@@ -223,17 +236,33 @@ static int poly_stage(smx_poly *p, size_t n, uint32_t **ops)
     return SMX_OK;
 }
 
-static inline void put_op(uint32_t *ops, size_t i, bool on, int note)
+// host-only op kind: all sound off, a kernel of its own between the allocator's launches
+enum { OP_SOUND_OFF = 7 };
+
+static inline void put_op(uint32_t *ops, size_t &n, uint32_t kind, int note)
 {
     const int m = note % 128;
-    ops[2 * i] = (uint32_t)m | (uint32_t)on << 8;
-    ops[2 * i + 1] = note_to_inc(m);
+    ops[2 * n] = (uint32_t)m | kind << 8;
+    ops[2 * n + 1] = note_to_inc(m);
+    n++;
 }
 
-// The n events staged in the current slot -> one H2D copy, then per POLY_EV_CAP events one launch of the allocator
-// (two kernels when the launch holds a note_on, one otherwise).  Stream order puts them after the blocks queued
-// before and ahead of the next one; the deferred fold of the last block (PolyPending) touches only its bus and
-// copies, never the arrays written here, so it stays owed to the next launch.
+// the op of a note event: a note_off under a down pedal sustains instead
+static inline void put_note(smx_poly *p, uint32_t *ops, size_t &n, bool on, int note)
+{
+    put_op(ops, n, on ? smx::POLY_OP_ON : (p->controllers && p->pedal) ? smx::POLY_OP_SUSTAIN : smx::POLY_OP_OFF, note);
+}
+
+static inline bool own_launch(uint32_t kind)
+{
+    return kind == smx::POLY_OP_RELEASE_SUSTAINED || kind == smx::POLY_OP_OFF_ALL || kind == OP_SOUND_OFF;
+}
+
+// The n ops staged in the current slot -> one H2D copy, then launches in order: runs of up to POLY_EV_CAP note ops
+// through the allocator (two kernels when the run holds a note_on, one otherwise), and every release-all and
+// all-sound-off in a launch of its own.  Stream order puts them after the blocks queued before
+// and ahead of the next one; the deferred fold of the last block (PolyPending) touches only its bus and copies,
+// never the arrays written here, so it stays owed to the next launch.
 static int poly_submit(smx_poly *p, size_t n)
 {
     if (n == 0) return SMX_OK;                               // nothing to do: nothing launched
@@ -243,13 +272,24 @@ static int poly_submit(smx_poly *p, size_t n)
     SMX_HIP(hipEventRecord(p->ev_stage[k], p->stream));
     p->ev_stage_busy[k] = true;
     p->ev_k ^= 1;
-    for (size_t e0 = 0; e0 < n; e0 += smx::POLY_EV_CAP) {
-        const uint32_t ne = (uint32_t)(n - e0 < (size_t)smx::POLY_EV_CAP ? n - e0 : (size_t)smx::POLY_EV_CAP);
-        bool any_on = false;
-        for (uint32_t i = 0; i < ne; i++) any_on |= (ops[2 * (e0 + i)] >> 8) != 0;
-        const int rv = smx::launch_poly_alloc(p->d, p->d_note2voice, p->d_voice_note, p->d_ops + 2 * e0, ne, any_on,
-                                              p->n, p->d_alloc, p->stream);
+    for (size_t e0 = 0; e0 < n;) {
+        const uint32_t kind0 = ops[2 * e0] >> 8;
+        int rv;
+        uint32_t ne = 1;
+        if (kind0 == OP_SOUND_OFF) {
+            rv = smx::launch_poly_sound_off(p->d, p->d_note2voice, p->d_voice_note, p->d_sustained, p->n_pad, p->stream);
+        } else {
+            bool any_on = false;
+            if (!own_launch(kind0)) {
+                ne = 0;
+                while (e0 + ne < n && ne < (uint32_t)smx::POLY_EV_CAP && !own_launch(ops[2 * (e0 + ne)] >> 8))
+                    any_on |= (ops[2 * (e0 + ne++)] >> 8) == smx::POLY_OP_ON;
+            }
+            rv = smx::launch_poly_alloc(p->d, p->d_note2voice, p->d_voice_note, p->d_sustained, p->d_ops + 2 * e0, ne,
+                                        any_on, p->n, p->d_alloc, p->stream);
+        }
         if (rv) return rv;
+        e0 += ne;
     }
     return SMX_OK;
 }
@@ -261,27 +301,68 @@ static int poly_note(smx_poly *p, int note, bool on, const char *what)
     uint32_t *ops;
     int rv = poly_stage(p, 1, &ops);
     if (rv) return rv;
-    put_op(ops, 0, on, note);
-    return poly_submit(p, 1);
+    size_t n = 0;
+    put_note(p, ops, n, on, note);
+    return poly_submit(p, n);
 }
 
 extern "C" int smx_poly_note_on(smx_poly *p, int note) { return poly_note(p, note, true, "smx_poly_note_on"); }
 extern "C" int smx_poly_note_off(smx_poly *p, int note) { return poly_note(p, note, false, "smx_poly_note_off"); }
 
-// process_midi dispatch (linux/synth.c:236-258) of a 3-byte message: 1 note_on, 0 note_off, -1 ignored
-static int midi_kind(const uint8_t *m)
+extern "C" uint32_t smx_poly_bend_mul(int bend14, int semitones)
 {
-    if (m[0] == 0x90) return m[2] != 0 ? 1 : 0;              // velocity 0: note_off
-    if (m[0] == 0x80) return 0;
-    return -1;
+    const int b = bend14 < 0 ? 0 : bend14 > 16383 ? 16383 : bend14;
+    const int r = semitones < 0 ? 0 : semitones > 24 ? 24 : semitones;
+    return (uint32_t)llround(65536.0 * exp2((double)r * (b - 8192) / (8192.0 * 12.0)));
+}
+
+static void poly_set_bend(smx_poly *p, int bend14, int range)
+{
+    p->bend14 = bend14;
+    p->bend_range = range;
+    p->bend_mul = smx_poly_bend_mul(bend14, range);
+}
+
+// One 3-byte message -> at most one op (appended at ops[n]); pedal and bend are updated on the host.
+// process_midi's dispatch (linux/synth.c:236-258) for 0x90 / 0x80, then, with the controllers on, channel 0's
+// CC 64 / 120 / 121 / 123 and pitch bend.  Everything else is ignored.
+static void poly_parse(smx_poly *p, const uint8_t *m, uint32_t *ops, size_t &n)
+{
+    if (m[0] == 0x90) { put_note(p, ops, n, m[2] != 0, m[1]); return; }      // velocity 0: note_off
+    if (m[0] == 0x80) { put_note(p, ops, n, false, m[1]); return; }
+    if (!p->controllers) return;
+    if (m[0] == 0xE0) { poly_set_bend(p, (m[1] & 0x7F) | (m[2] & 0x7F) << 7, p->bend_range); return; }
+    if (m[0] != 0xB0) return;
+    switch (m[1]) {
+    case 64: {                                               // sustain pedal
+        const bool down = m[2] >= 64;
+        if (down == p->pedal) return;
+        p->pedal = down;
+        if (!down) put_op(ops, n, smx::POLY_OP_RELEASE_SUSTAINED, 0);
+        return;
+    }
+    case 120: put_op(ops, n, OP_SOUND_OFF, 0); return;      // all sound off
+    case 121:                                                // reset all controllers: pedal up, bend to centre
+        if (p->pedal) { p->pedal = false; put_op(ops, n, smx::POLY_OP_RELEASE_SUSTAINED, 0); }
+        poly_set_bend(p, 8192, p->bend_range);
+        return;
+    case 123:                                                // all notes off: sustained under a down pedal
+        put_op(ops, n, p->pedal ? smx::POLY_OP_SUSTAIN_ALL : smx::POLY_OP_OFF_ALL, 0);
+        return;
+    default: return;
+    }
 }
 
 extern "C" int smx_poly_midi_event(smx_poly *p, const uint8_t *msg, size_t size)
 {
     if (!p || (size && !msg)) { set_error("smx_poly_midi_event: bad args"); return SMX_E_ARG; }
     if (size != 3) return SMX_OK;
-    const int kind = midi_kind(msg);
-    return kind < 0 ? SMX_OK : poly_note(p, msg[1], kind == 1, "smx_poly_midi_event");
+    uint32_t *ops;
+    int rv = poly_stage(p, 1, &ops);
+    if (rv) return rv;
+    size_t n = 0;
+    poly_parse(p, msg, ops, n);
+    return poly_submit(p, n);
 }
 
 extern "C" int smx_poly_midi_events(smx_poly *p, const uint8_t *msgs3, size_t n_events)
@@ -292,11 +373,31 @@ extern "C" int smx_poly_midi_events(smx_poly *p, const uint8_t *msgs3, size_t n_
     int rv = poly_stage(p, n_events, &ops);
     if (rv) return rv;
     size_t n = 0;
-    for (size_t i = 0; i < n_events; i++) {
-        const int kind = midi_kind(msgs3 + 3 * i);
-        if (kind >= 0) put_op(ops, n++, kind == 1, msgs3[3 * i + 1]);
-    }
+    for (size_t i = 0; i < n_events; i++) poly_parse(p, msgs3 + 3 * i, ops, n);
     return poly_submit(p, n);
+}
+
+extern "C" int smx_poly_set_controllers(smx_poly *p, int on)
+{
+    if (!p) { set_error("smx_poly_set_controllers: null bank"); return SMX_E_ARG; }
+    p->controllers = on != 0;
+    return SMX_OK;
+}
+
+extern "C" int smx_poly_set_bend_range(smx_poly *p, int semitones)
+{
+    if (!p || semitones < 0 || semitones > 24) { set_error("smx_poly_set_bend_range: semitones=%d (0..24)", semitones); return SMX_E_ARG; }
+    poly_set_bend(p, p->bend14, semitones);
+    return SMX_OK;
+}
+
+extern "C" int smx_poly_read_sustain(smx_poly *p, uint8_t sustained[128])
+{
+    if (!p || !sustained) { set_error("smx_poly_read_sustain: bad args"); return SMX_E_ARG; }
+    SMX_HIP(hipSetDevice(p->device));
+    SMX_HIP(hipStreamSynchronize(p->stream));
+    SMX_HIP(hipMemcpy(sustained, p->d_sustained, 128, hipMemcpyDeviceToHost));
+    return SMX_OK;
 }
 
 extern "C" int smx_poly_read_notes(smx_poly *p, int32_t note2voice[128])

@@ -18,11 +18,23 @@
 //     a held note releases one and picks one), so with E <= 64 events fewer than 2E <= POLY_LIST voices are ever
 //     touched before a pick: a full list never runs dry, and a list that is not full holds every such voice.
 //     The dirty set and the note map are written back at the end.
+//
+// Controllers.  The op word is note | kind << 8.  Besides note_off / note_on, a note_off under a
+// down pedal (OP_SUSTAIN) and "sustain every mapped note" (OP_SUSTAIN_ALL, CC 123 under the pedal) only set bits of
+// sustained[128], which sits in LDS next to n2v.  The release-alls -- pedal up (OP_RELEASE_SUSTAINED) and CC 123 with
+// the pedal up (OP_OFF_ALL) -- may touch up to 128 voices, which would break the 2-per-event bound above and the
+// dirty set.  The host therefore gives each of them a launch of its own (no scan: nothing is picked).  There the
+// dirty set is empty, note2voice is injective, and a release writes only gate and voice_note of its own voice, so
+// the <= 128 releases are independent: wave 0 applies them in parallel, two notes per lane, straight to HBM.  All
+// sound off (CC 120) is poly_sound_off below, a grid-stride kernel of its own, queued in stream order.
 #include "smx_common.h"
 
 namespace {
 
 enum { ENV_IDLE = 0, ENV_R = 4 };
+enum { OP_OFF = smx::POLY_OP_OFF, OP_ON = smx::POLY_OP_ON, OP_SUSTAIN = smx::POLY_OP_SUSTAIN,
+       OP_SUSTAIN_ALL = smx::POLY_OP_SUSTAIN_ALL, OP_RELEASE_SUSTAINED = smx::POLY_OP_RELEASE_SUSTAINED,
+       OP_OFF_ALL = smx::POLY_OP_OFF_ALL };
 enum { POLY_LIST = 128, SCAN_NT = 512, SCAN_BUF = 1024, APPLY_NT = 1024 };
 static_assert(POLY_LIST >= 2 * smx::POLY_EV_CAP, "the lists must outlast 2 touches per event");
 
@@ -153,7 +165,8 @@ struct ApplyArgs {
     const uint32_t *level;
     int32_t *note2voice;             // [128], -1: none
     int32_t *voice_note;             // [n_pad], -1: none
-    const uint32_t *ops;             // n_ops pairs (note | on << 8, inc of the note)
+    uint8_t *sustained;              // [128], 1: the note is held by the pedal
+    const uint32_t *ops;             // n_ops pairs (note | kind << 8, inc of the note)
     uint32_t n_ops;
     uint32_t n_lists;                // workgroups of the scan (0: no scan ran -- the launch has no note_on)
     ScanOut lists;
@@ -171,6 +184,7 @@ void poly_alloc_apply(ApplyArgs A)
     __shared__ uint32_t Dv[POLY_LIST], Dinc[POLY_LIST], Dgate[POLY_LIST], Dstage[POLY_LIST], Dlevel[POLY_LIST];
     __shared__ int32_t Dnote[POLY_LIST];
     __shared__ int32_t n2v[128];
+    __shared__ uint8_t sus[128];
     __shared__ uint32_t s_nd;
     const uint32_t tid = threadIdx.x;
     const uint32_t G = A.n_lists;
@@ -219,10 +233,26 @@ void poly_alloc_apply(ApplyArgs A)
         for (uint32_t i = tid; i < POLY_LIST; i += APPLY_NT) LK[i] = NO_KEY;
     }
     for (uint32_t i = tid; i < POLY_LIST; i += APPLY_NT) { fdead[i] = 0; kdead[i] = 0; }
-    for (uint32_t i = tid; i < 128; i += APPLY_NT) n2v[i] = A.note2voice[i];
+    for (uint32_t i = tid; i < 128; i += APPLY_NT) { n2v[i] = A.note2voice[i]; sus[i] = A.sustained[i]; }
     if (tid == 0) s_nd = 0;
     __syncthreads();
     if (tid >= 64) return;
+
+    // a release-all, alone in its launch (the host guarantees it): independent releases of distinct voices
+    const uint32_t kind0 = (A.ops[0] >> 8) & 7u;
+    if (A.n_ops == 1 && (kind0 == OP_RELEASE_SUSTAINED || kind0 == OP_OFF_ALL)) {
+        for (uint32_t m = tid; m < 128; m += 64) {
+            const int32_t v = n2v[m];
+            if (v >= 0 && (kind0 == OP_OFF_ALL || sus[m])) {
+                A.gate[v] = 0;
+                A.voice_note[v] = -1;
+                n2v[m] = -1;
+            }
+            A.note2voice[m] = n2v[m];
+            A.sustained[m] = 0;
+        }
+        return;
+    }
 
     // (b) the events, in order, by wave 0.  Lane l looks after dirty entries / list positions l and l + 64.
     const uint32_t lane = tid;
@@ -251,7 +281,7 @@ void poly_alloc_apply(ApplyArgs A)
     auto release = [&](int32_t note) {               // note_off of a mapped note
         const uint32_t v = (uint32_t)n2v[note];
         const uint32_t d = touch(v);
-        if (lane == 0) { Dgate[d] = 0; Dnote[d] = -1; n2v[note] = -1; }
+        if (lane == 0) { Dgate[d] = 0; Dnote[d] = -1; n2v[note] = -1; sus[note] = 0; }
         wsync();
     };
     auto pick = [&]() -> uint32_t {
@@ -276,14 +306,20 @@ void poly_alloc_apply(ApplyArgs A)
     for (uint32_t e = 0; e < A.n_ops; e++) {
         const uint32_t op = A.ops[2 * e], ninc = A.ops[2 * e + 1];
         const int32_t note = (int32_t)(op & 127u);
-        const bool on = (op >> 8) & 1u;
-        if (n2v[note] >= 0) release(note);          // note_off, or a note_on of a held note
-        if (!on) continue;
+        const uint32_t kind = (op >> 8) & 7u;
+        if (kind == OP_SUSTAIN || kind == OP_SUSTAIN_ALL) {          // the pedal keeps the voice: gate and maps stay
+            for (uint32_t m = lane; m < 128; m += 64)
+                if ((kind == OP_SUSTAIN_ALL || m == (uint32_t)note) && n2v[m] >= 0) sus[m] = 1;
+            wsync();
+            continue;
+        }
+        if (n2v[note] >= 0) release(note);          // note_off, or a note_on of a held (or sustained) note
+        if (kind != OP_ON) continue;
         const uint32_t v = pick();
         if (v == NO_VOICE) continue;                 // unreachable for n >= 1 (every voice is free or has a key)
         const uint32_t d = touch(v);
         if (lane == 0) {
-            if (Dnote[d] >= 0) n2v[Dnote[d]] = -1;
+            if (Dnote[d] >= 0) { n2v[Dnote[d]] = -1; sus[Dnote[d]] = 0; }
             if (Dgate[d]) Dstage[d] = ENV_R;         // a held voice is stolen: the block start re-attacks it
             Dinc[d] = ninc; Dgate[d] = 1; Dnote[d] = note; n2v[note] = (int32_t)v;
         }
@@ -296,7 +332,21 @@ void poly_alloc_apply(ApplyArgs A)
         const uint32_t v = Dv[i];
         A.inc[v] = Dinc[i]; A.gate[v] = Dgate[i]; A.stage[v] = Dstage[i]; A.voice_note[v] = Dnote[i];
     }
-    for (uint32_t i = lane; i < 128; i += 64) A.note2voice[i] = n2v[i];
+    for (uint32_t i = lane; i < 128; i += 64) { A.note2voice[i] = n2v[i]; A.sustained[i] = sus[i]; }
+}
+
+// All sound off (CC 120): every voice idle, silent and free; both maps and the sustained bits cleared.  inc, phase,
+// y and the patch are not touched.  16 B written per voice.
+__global__ __launch_bounds__(256)
+void poly_sound_off(uint32_t *__restrict__ gate, uint32_t *__restrict__ stage, uint32_t *__restrict__ level,
+                    int32_t *__restrict__ voice_note, int32_t *__restrict__ note2voice, uint8_t *__restrict__ sustained,
+                    uint32_t n_pad)
+{
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x < 128) { note2voice[threadIdx.x] = -1; sustained[threadIdx.x] = 0; }
+    for (uint32_t v = t; v < n_pad; v += gridDim.x * 256) {
+        gate[v] = 0; stage[v] = ENV_IDLE; level[v] = 0; voice_note[v] = -1;
+    }
 }
 
 }  // namespace
@@ -315,8 +365,9 @@ size_t poly_alloc_scratch_bytes(uint32_t n)
     return g * POLY_LIST * 8 + g * POLY_LIST * 4 + g * 4;
 }
 
-int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, const uint32_t *d_ops,
-                      uint32_t n_ops, bool any_on, uint32_t n, void *d_scratch, hipStream_t stream)
+int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, uint8_t *d_sustained,
+                      const uint32_t *d_ops, uint32_t n_ops, bool any_on, uint32_t n, void *d_scratch,
+                      hipStream_t stream)
 {
     if (n_ops == 0 || n_ops > POLY_EV_CAP || n == 0 || n >= 0x80000000u) {
         set_error("launch_poly_alloc: n_ops=%u n=%u", n_ops, n);
@@ -334,7 +385,7 @@ int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voi
         hipLaunchKernelGGL(poly_alloc_scan, dim3(gx), dim3(SCAN_NT), 0, stream, p.inc, p.gate, p.stage, p.level,
                            n, tpw, lists);
         SMX_HIP(hipGetLastError());
-        ApplyArgs a{p.inc, p.gate, p.stage, p.level, d_note2voice, d_voice_note, d_ops, n_ops, gx, lists};
+        ApplyArgs a{p.inc, p.gate, p.stage, p.level, d_note2voice, d_voice_note, d_sustained, d_ops, n_ops, gx, lists};
         uint32_t gp = 1;
         while (gp < gx) gp <<= 1;
         static const bool lds_ok = hipFuncSetAttribute((const void *)poly_alloc_apply,
@@ -343,9 +394,21 @@ int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voi
         if (!lds_ok) { set_error("launch_poly_alloc: cannot raise the LDS limit of poly_alloc_apply"); return SMX_E_NOGPU; }
         hipLaunchKernelGGL(poly_alloc_apply, dim3(1), dim3(APPLY_NT), (size_t)gp * POLY_LIST * 8, stream, a);
     } else {
-        ApplyArgs a{p.inc, p.gate, p.stage, p.level, d_note2voice, d_voice_note, d_ops, n_ops, 0, lists};
+        ApplyArgs a{p.inc, p.gate, p.stage, p.level, d_note2voice, d_voice_note, d_sustained, d_ops, n_ops, 0, lists};
         hipLaunchKernelGGL(poly_alloc_apply, dim3(1), dim3(APPLY_NT), (size_t)POLY_LIST * 8, stream, a);
     }
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+}
+
+int launch_poly_sound_off(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, uint8_t *d_sustained,
+                          uint32_t n_pad, hipStream_t stream)
+{
+    if (n_pad == 0 || (n_pad & 1023)) { set_error("launch_poly_sound_off: n_pad=%u", n_pad); return SMX_E_ARG; }
+    const uint32_t blocks = n_pad / 256;
+    const uint32_t gx = blocks < 2048u ? blocks : 2048u;     // 8 workgroups per CU, grid-stride above that
+    hipLaunchKernelGGL(poly_sound_off, dim3(gx), dim3(256), 0, stream, p.gate, p.stage, p.level, d_voice_note,
+                       d_note2voice, d_sustained, n_pad);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
 }

@@ -54,7 +54,8 @@ template <int NT, bool F64>
 __global__ __launch_bounds__(NT)
 void poly_bank_kernel(smx::PolyArrays p, int32_t *__restrict__ slots /* [POLY_SLOTS][128], zero */,
                       int32_t *__restrict__ own_bus /* cleared here when the fold of THIS launch is deferred; or nullptr */,
-                      PolyOwed owed, uint32_t n_pad, uint32_t nframes_rt /* <= 64 */)
+                      PolyOwed owed, uint32_t n_pad, uint32_t nframes_rt /* <= 64 */,
+                      uint32_t bend_mul /* Q16 pitch bend, 65536: unbent */)
 {
     __shared__ int32_t M[POLY_ROWS][65];
     const uint32_t nframes = F64 ? 64u : nframes_rt;
@@ -92,8 +93,12 @@ void poly_bank_kernel(smx::PolyArrays p, int32_t *__restrict__ slots /* [POLY_SL
     __syncthreads();
 
     for (;;) {
-      if (w.inc) {                                           // 0 == off: frozen, silent
-        const uint32_t inc = w.inc;
+      // pitch bend: a kernel argument, so the test is scalar and the unbent path keeps its instructions; once per
+      // voice row, outside the frame loop.  Only the phase sees the bent increment.
+      uint32_t inc_eff = w.inc;
+      if (bend_mul != 65536u) inc_eff = (uint32_t)(((uint64_t)inc_eff * bend_mul) >> 16);
+      if (inc_eff) {                                         // 0 == off (or bent to 0): frozen, silent
+        const uint32_t inc = inc_eff;
         uint32_t phase = w.phase, level = w.level, stage = w.stage;
         float y = w.y;
         const float a = w.a;
@@ -243,10 +248,10 @@ void poly_finalize_kernel(int32_t *__restrict__ slots, int32_t *__restrict__ bus
 
 template <int NT>
 void poly_launch(bool f64, uint32_t gx, hipStream_t stream, const smx::PolyArrays &p, int32_t *slots, int32_t *own_bus,
-                 PolyOwed owed, uint32_t n_pad, uint32_t nframes)
+                 PolyOwed owed, uint32_t n_pad, uint32_t nframes, uint32_t bend_mul)
 {
-    if (f64) hipLaunchKernelGGL((poly_bank_kernel<NT, true>), dim3(gx), dim3(NT), 0, stream, p, slots, own_bus, owed, n_pad, nframes);
-    else     hipLaunchKernelGGL((poly_bank_kernel<NT, false>), dim3(gx), dim3(NT), 0, stream, p, slots, own_bus, owed, n_pad, nframes);
+    if (f64) hipLaunchKernelGGL((poly_bank_kernel<NT, true>), dim3(gx), dim3(NT), 0, stream, p, slots, own_bus, owed, n_pad, nframes, bend_mul);
+    else     hipLaunchKernelGGL((poly_bank_kernel<NT, false>), dim3(gx), dim3(NT), 0, stream, p, slots, own_bus, owed, n_pad, nframes, bend_mul);
 }
 
 }  // namespace
@@ -267,7 +272,7 @@ int launch_poly_flush(PolyPending *pend, hipStream_t stream)
 }
 
 int launch_poly_bank(const PolyArrays &p, int32_t *d_bus_lr, int32_t *d_slots, uint32_t n_pad,
-                     uint32_t nframes, hipStream_t stream, PolyPending *pend)
+                     uint32_t nframes, hipStream_t stream, PolyPending *pend, uint32_t bend_mul)
 {
     if (n_pad == 0 || (n_pad & 1023) || nframes == 0 || nframes > 64) {
         set_error("launch_poly_bank: n_pad=%u nframes=%u", n_pad, nframes);
@@ -294,9 +299,9 @@ int launch_poly_bank(const PolyArrays &p, int32_t *d_bus_lr, int32_t *d_slots, u
         own_bus = d_bus_lr;
     }
     const bool f64 = nframes == 64;
-    if (nt == 256)      poly_launch<256>(f64, gx, stream, p, slots, own_bus, owed, n_pad, nframes);
-    else if (nt == 512) poly_launch<512>(f64, gx, stream, p, slots, own_bus, owed, n_pad, nframes);
-    else                poly_launch<1024>(f64, gx, stream, p, slots, own_bus, owed, n_pad, nframes);
+    if (nt == 256)      poly_launch<256>(f64, gx, stream, p, slots, own_bus, owed, n_pad, nframes, bend_mul);
+    else if (nt == 512) poly_launch<512>(f64, gx, stream, p, slots, own_bus, owed, n_pad, nframes, bend_mul);
+    else                poly_launch<1024>(f64, gx, stream, p, slots, own_bus, owed, n_pad, nframes, bend_mul);
     if (pend) {
         pend->slots = slots;
         pend->bus = d_bus_lr;

@@ -156,17 +156,33 @@ struct PolyPending {
 size_t poly_scratch_bytes();
 size_t poly_bus_bytes();
 int launch_poly_flush(PolyPending *pend, hipStream_t stream);
+// bend_mul: the pitch bend's Q16 increment multiplier (65536: unbent); every voice's phase advances by
+// (inc * bend_mul) >> 16 (mod 2^32), the stored inc is not changed.
 int launch_poly_bank(const PolyArrays &p, int32_t *d_bus_lr, int32_t *d_slots, uint32_t n_pad,
-                     uint32_t nframes, hipStream_t stream, PolyPending *pend = nullptr);
+                     uint32_t nframes, hipStream_t stream, PolyPending *pend = nullptr, uint32_t bend_mul = 65536u);
 // Note events of the poly bank (poly_alloc.hip): at most POLY_EV_CAP events per launch, as pairs
-// (note | on << 8, note_to_inc(note)) in device memory; note2voice[128] / voice_note[n_pad] hold -1 for none.
+// (note | kind << 8, note_to_inc(note)) in device memory; note2voice[128] / voice_note[n_pad] hold -1 for none,
+// sustained[128] 1 for a note the pedal holds.  A launch with a POLY_OP_RELEASE_SUSTAINED or POLY_OP_OFF_ALL holds
+// that op alone (n_ops == 1).
 // any_on == false (no note_on among them): no pass over the bank.  n < 2^31 (the index is 31 bits of the key).
 // d_scratch: poly_alloc_scratch_bytes(n) bytes (the scan's per-workgroup lists).
 enum { POLY_EV_CAP = 64, POLY_ALLOC_MAX_WG = 128 };
+enum {
+    POLY_OP_OFF = 0, POLY_OP_ON = 1,
+    POLY_OP_SUSTAIN = 2,                // note_off under a down pedal: sustained[m] = 1 if m is mapped
+    POLY_OP_SUSTAIN_ALL = 3,            // CC 123 under a down pedal: every mapped note sustained
+    POLY_OP_RELEASE_SUSTAINED = 4,      // pedal up: note_off of every sustained note; alone in its launch
+    POLY_OP_OFF_ALL = 5,                // CC 123 with the pedal up: note_off of every mapped note; alone in its launch
+};
 uint32_t poly_alloc_lists(uint32_t n);
 size_t poly_alloc_scratch_bytes(uint32_t n);
-int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, const uint32_t *d_ops,
-                      uint32_t n_ops, bool any_on, uint32_t n, void *d_scratch, hipStream_t stream);
+int launch_poly_alloc(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, uint8_t *d_sustained,
+                      const uint32_t *d_ops, uint32_t n_ops, bool any_on, uint32_t n, void *d_scratch,
+                      hipStream_t stream);
+// All sound off (CC 120): gate, stage, level = 0 and voice_note = -1 over n_pad voices, note2voice and sustained
+// cleared.
+int launch_poly_sound_off(const PolyArrays &p, int32_t *d_note2voice, int32_t *d_voice_note, uint8_t *d_sustained,
+                          uint32_t n_pad, hipStream_t stream);
 
 // Noise-shaped PWM bank (pwm_bank.hip): device SoA arrays, n_pad entries each.
 struct PwmArrays {
